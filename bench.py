@@ -8,12 +8,16 @@ Workload at N=1 = BASELINE.json configs[1]: ~1 Gbp synthetic bacterial index (25
 N>1: one process per GPU, index replicated, each rank classifies its own 10 M reads (weak scaling,
 no data-path collective); value = all reads / max-over-ranks time.
 
-Also reported on the same JSON line:
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints the line: the headline
+figure, ms_per_step and the step's stage times, nothing else.  --dump-outputs DIR also writes what the timed entry returned in
+the last timed step (dump_outputs).  --full adds everything else, on the same JSON line:
   roofline     — dominant kernel (k_search_chains): algorithmic bytes (counted exactly by
                  the C oracle on a sample and scaled per read) / kernel time from HIP events inside the library.
-  cpu_baseline — the REAL reference binary (oracle/_ref/centrifuger, compiled from /root/reference in the dev
-                 container) on this box's host cores, on a bounded sample of the same reads, and a byte-level
+  cpu_baseline — the REAL reference binary (oracle/_ref/centrifuger, compiled from the reference's sources by
+                 oracle/Makefile) on this box's host cores, on a bounded sample of the same reads, and a byte-level
                  TSV parity check GPU vs reference on that sample.
+  parity with the C oracle, the SDUST and other-layout legs, host-memory entries, the command line end to end, live
+  PMC passes, and the other configurations (PE, long reads, strain workloads; the 40 Gbp legs with --with-40gbp).
 """
 import argparse
 import hashlib
@@ -54,7 +58,7 @@ def _r(v, nd=4):
     return float(f"{f:.{nd}g}")
 
 
-def compact_line(out):
+def compact_line(out, plain=False):
     """The line the driver reads: the contract's keys, `roofline` and `cpu_baseline` as flat objects of scalars, the parity booleans and ONE scalar
     per sub-result - a few hundred bytes each, <= COMPACT_LIMIT in all.  Everything else (notes, per-kernel counters, iteration mixes) goes to the
     detail file / stderr (`emit_line`).  tests/test_bench_static.py builds this from stored detail objects and checks size, keys and finiteness."""
@@ -137,6 +141,9 @@ def compact_line(out):
         else:
             sub[name] = {"error": str(o.get("error"))[:120]}
     line["sub_results"] = sub
+    for k, v in (("roofline", roof), ("parity", par), ("sub_results", sub)):
+        if plain and not v:         # a plain run measures none of these: no empty objects on its line
+            del line[k]
     if out.get("detail"):
         line["detail"] = out["detail"]
     s = json.dumps(line, allow_nan=False, separators=(",", ":"))
@@ -157,6 +164,9 @@ def emit_line(out, args=None):
     full = json.dumps(out)
     if (args is not None and (getattr(args, "inner", False) or getattr(args, "sub_result", False))) or os.environ.get("CFR_BENCH_FULL_LINE") == "1":
         print(full, flush=True)
+        return
+    if args is not None and not getattr(args, "full", True):      # a plain run: the line and nothing else
+        print(compact_line(out, plain=True), flush=True)
         return
     path = os.environ.get("CFR_BENCH_DETAIL")
     if not path:
@@ -374,6 +384,47 @@ def make_long_reads_gpu(torch, cat_d, starts, n_reads, seed, device, len_lo=5000
     offs = torch.zeros(n_reads + 1, dtype=torch.int64, device=device)
     offs[1:] = torch.cumsum(ll, 0)
     return bases, offs
+
+
+DUMP_BUDGET = 48 << 20      # bytes of float64 data --dump-outputs writes at most (the limit is 64 MB in all)
+
+
+def dump_outputs(path, results, matches, k, compact, dev=None, seed=0):
+    """--dump-outputs: what the timed entry handed its caller in the last timed step, per read, as float64 .npy files under path:
+    the result fields (score.npy, secondary_score.npy, hit_length.npy, query_length.npy, n_match.npy) and the k match slots of each
+    read (match_id.npy, match_taxid.npy, match_kind.npy: shape (reads, k), -1 past n_match).  The whole batch when it fits
+    DUMP_BUDGET, else a sample of reads drawn with `seed`; read_index.npy says which.  compact: the arrays of
+    cfr_classify_batch_resident_compact (the reads it flagged CFR_COMPACT_WIDE are taken from dev.compact_wide()); else the wide ones."""
+    from centrifuger_amd import capi
+    n = len(results)
+    fields = ("score", "secondary_score", "hit_length", "query_length", "n_match")
+    m = min(n, DUMP_BUDGET // (8 * (1 + len(fields) + 3 * k)))
+    sel = np.arange(n) if m == n else np.sort(np.random.default_rng(seed).choice(n, m, replace=False))
+    if compact:
+        cres = results[sel]
+        cmat = matches[:n * k].reshape(n, k)[sel].reshape(-1)
+        wide = None
+        if ((cres["flags"] & capi.COMPACT_WIDE) != 0).any():
+            widx, wres, wmat = dev.compact_wide()
+            pos = np.searchsorted(sel, widx)
+            ok = (pos < m) & (sel[np.minimum(pos, m - 1)] == widx)
+            wide = (pos[ok], wres[ok], wmat)
+        res, mat = capi.expand_compact(cres, cmat, k, wide=wide)
+    else:
+        res, mat = results[sel], matches
+    cols = {"read_index": sel}
+    for f in fields:
+        cols[f] = res[f]
+    used = np.arange(k)[None, :] < np.minimum(res["n_match"].astype(np.int64), k)[:, None]
+    slot = res["match_begin"].astype(np.int64)[:, None] + np.arange(k)[None, :]
+    for f in ("id", "taxid", "kind"):
+        v = np.full((m, k), -1.0)
+        v[used] = mat[f][slot[used]]
+        cols["match_" + f] = v
+    os.makedirs(path, exist_ok=True)
+    for name, v in cols.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(v, dtype=np.float64))
+    log(f"outputs of the last timed step: {m} of {n} reads, {len(cols)} arrays in {path}")
 
 
 BYTES_PER_RANDOM_REQUEST = 128.0     # profiles/r2a_gather_calib.json
@@ -988,6 +1039,8 @@ def protein_mode(torch, capi, args, device):
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     results, matches = res_pin.array, mat_pin.array
+    if args.dump_outputs and not getattr(args, "inner", False):
+        dump_outputs(args.dump_outputs, results, matches, k, False, seed=args.seed)
     out = {"metric": "classified reads/sec (150 bp, translated search against a protein index)", "value": n * args.steps / el, "unit": "reads/s", "n_gpus": 1,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1000 * el / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
            "dtype": "u64", "data": "synthetic",
@@ -997,7 +1050,7 @@ def protein_mode(torch, capi, args, device):
            "stage_ms": {kk: float(np.mean([getattr(s_, kk) for s_ in kst])) for kk in ("search_ms", "adjust_ms", "rows_ms", "locate_ms", "tail_ms", "total_ms")}}
     if os.path.exists(prefix + ".build.json"):
         out["index"] = json.load(open(prefix + ".build.json"))
-    if getattr(args, "inner", False):
+    if getattr(args, "inner", False) or not args.full:
         emit_line(out, args)
         dev.close()
         return
@@ -1090,7 +1143,7 @@ def sub_config_40gbp(args, cfg):
             need.append(f"{args.cache}: {disk/1e9:.0f} GB free (text 40 GB + index files 17 GB + samples)")
         if need:
             return {"skipped": "; ".join(need)}
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", cfg, "--sub-result", "--cache", args.cache, "--seed", str(args.seed)] + (["--no-pmc"] if args.no_pmc else [])
+        cmd = [sys.executable, os.path.abspath(__file__), "--config", cfg, "--full", "--sub-result", "--cache", args.cache, "--seed", str(args.seed)] + (["--no-pmc"] if args.no_pmc else [])
         if cfg == "cfg5":
             cmd.append("--no-cpu-baseline")      # (20 000 long reads through the reference binary at 40 Gbp take minutes; parity of this leg = the C oracle on 4000 reads)
         env = dict(os.environ)
@@ -1127,7 +1180,7 @@ def sub_config_40gbp(args, cfg):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 3; 8 with --config cfg5)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--species", type=int, default=50)
     ap.add_argument("--strains", type=int, default=5)
@@ -1168,7 +1221,12 @@ def main():
     ap.add_argument("--divergence-model", choices=["star", "tree"], default="star", help="synth.make_genomes model (tree: strain k descends from strain (k-1)//2)")
     ap.add_argument("--inner-dust", action="store_true", help=argparse.SUPPRESS)   # child of the SDUST PMC passes: the inner step with the pre-step on
     ap.add_argument("--sub-result", action="store_true", help=argparse.SUPPRESS)   # child of the default run: one BASELINE config as a compact sub-result
-    ap.add_argument("--no-40gbp", action="store_true", help="skip the cfg4 / cfg5 legs (40 Gbp index on this GPU) of the default run")
+    ap.add_argument("--no-40gbp", action="store_true", help="skip the cfg4 / cfg5 legs (40 Gbp index on this GPU) of a --full run (the default: see --with-40gbp)")
+    ap.add_argument("--with-40gbp", action="store_true", help="--full: also the cfg4 / cfg5 legs on a 40 Gbp index (~8 minutes more on a fresh box: the index is written first)")
+    ap.add_argument("--full", action="store_true", help="besides the timed steps: CPU baseline, parity checks, SDUST / other-layout / host-memory legs, live PMC "
+                                                        "roofline, the command line end to end and the other configurations (a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed entry returned in the last one as float64 "
+                                                                          "DIR/<name>.npy (dump_outputs: the whole batch, or a seeded sample of reads, <= 48 MB)")
     args = ap.parse_args()
     if args.config == "cfg3":
         args.mode = "pe"
@@ -1180,8 +1238,10 @@ def main():
         args.index_gbp, args.mode = args.index_gbp or 40.0, "long"
         if args.reads == 10_000_000:
             args.reads = 312_500
-        if args.steps == 3:
+        if args.steps is None:
             args.steps = 8          # 8 x 312 500 = cfg5's 2.5 M long reads per rank
+    if args.steps is None:
+        args.steps = 3
     if args.index_gbp >= 4 and args.cpu_sample == 2_000_000:
         args.cpu_sample = 400_000       # the reference loads a 40 Gbp index for minutes per run: a smaller sample, no thread sweep
     if args.config in ("cfg4", "cfg5"):
@@ -1290,8 +1350,9 @@ def main():
         """first nsel reads of flat device buffer t as (bases, offsets) numpy"""
         hi = int(offs_h[nsel])
         return t.reshape(-1)[:hi].cpu().numpy(), offs_h[:nsel + 1].copy()
-    res_pin = capi.PinnedArray(args.reads, capi.RESULT_DTYPE)     # cfr_host_alloc: D2H at PCIe rate
-    mat_pin = capi.PinnedArray(args.reads * k, capi.MATCH_DTYPE)
+    wide_n = args.reads if args.full or args.results == "wide" else 0      # (the wide arrays: the timed entry's with --results wide, the checks' with --full)
+    res_pin = capi.PinnedArray(wide_n, capi.RESULT_DTYPE)     # cfr_host_alloc: D2H at PCIe rate
+    mat_pin = capi.PinnedArray(wide_n * k, capi.MATCH_DTYPE)
     results, matches = res_pin.array, mat_pin.array
     # the timed entry: cfr_classify_batch_resident_compact (same results, 20 + 12 bytes per read / match slot instead of
     # 40 + 24: the step's D2H halves) unless --results wide; the other one is timed as a sub-result
@@ -1331,14 +1392,41 @@ def main():
     elapsed = time.perf_counter() - t0
     from centrifuger_amd import shard
     elapsed = shard.max_over_ranks(elapsed, dist=dist, device=None if share_gpu else device)   # the job is as slow as its slowest rank
-    widen()
-    classified = int((results["n_match"] > 0).sum())
+    if args.dump_outputs and rank == 0 and not args.inner:
+        dump_outputs(args.dump_outputs, *((cres_pin.array, cmat_pin.array) if entry["compact"] else (results, matches)), k, entry["compact"], dev, args.seed)
     if args.inner:      # run under rocprofv3 by the parent bench: the timed launches are all it is for
         if rank == 0:
             print(json.dumps({"inner": True, "reads": args.reads, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1000.0 * elapsed / args.steps,
                               "search_ms": float(np.mean([s.search_ms for s in kstats])), "tail_ms": float(np.mean([s.tail_ms for s in kstats])),
                               "device_total_ms": float(np.mean([s.total_ms for s in kstats]))}), flush=True)
         return
+    total_reads = args.reads * args.steps * world
+    value = total_reads / elapsed
+    out = {
+        "metric": "classified reads/sec (150 bp)", "value": value, "unit": "read pairs/s" if paired else "reads/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": 1000.0 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "u64", "data": "synthetic",
+        "config": {"workload": f"{info.n/1e9:.2f} Gbp synthetic index ({args.species}x{args.strains}x{args.genome_len/1e6:g} Mbp), " +
+                               (f"{args.reads} long reads (5-20 kbp, mean {total_bases/args.reads:.0f} bp) per step per GPU, -k {k}, inputs resident in HBM" if longmode else
+                                f"{args.reads} x {'2x' if paired else ''}{args.read_len} bp {'PE' if paired else 'SE'} reads per step per GPU, -k {k}, inputs resident in HBM"),
+                   "index_bp": int(info.n), "reads_per_step_per_gpu": args.reads, "read_len": args.read_len,
+                   "parallelism": f"reads sharded over {world} GPU(s), index replicated, no collective",
+                   "numa_node_of_rank0": numa,
+                   "timed_entry": ("cfr_classify_batch_resident_compact (20 + 12 bytes per read / match slot to the host)" if entry["compact"]
+                                   else "cfr_classify_batch_resident (40 + 24 bytes per read / match slot to the host)")},
+        "stage_ms": {k: float(np.mean([getattr(s, k) for s in kstats])) for k in
+                     ("pack_ms", "search_ms", "adjust_ms", "rows_ms", "locate_ms", "tail_ms", "total_ms")},
+    }
+    if not args.full:       # a plain run: the line of the timed steps and nothing else
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            out["classified_fraction"] = int(((cres_pin.array if entry["compact"] else results)["n_match"] > 0).sum()) / args.reads
+            emit_line(out, args)
+        return
+    widen()
+    classified = int((results["n_match"] > 0).sum())
     # the same step with the SDUST pre-step on the device (private copy of the reads + k_dust); never `value`
     dev.set_dust(True)
     step()
@@ -1380,29 +1468,11 @@ def main():
     if rank != 0:
         return
 
-    total_reads = args.reads * args.steps * world
-    value = total_reads / elapsed
     search_ms = float(np.mean([s.search_ms for s in kstats]))
-    out = {
-        "metric": "classified reads/sec (150 bp)", "value": value, "unit": "read pairs/s" if paired else "reads/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": 1000.0 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "u64", "data": "synthetic",
-        "index_on_ranks": {"ranks": len(ranks_index), "mapped_bytes_min": min(r_[0] for r_ in ranks_index), "copied_bytes_max": max(r_[1] for r_ in ranks_index),
-                           "device_image_bytes": ranks_index[0][2],
-                           "every_rank_maps_the_file": all(r_[0] > 0 and r_[1] == 0 for r_ in ranks_index)},
-        "config": {"workload": f"{info.n/1e9:.2f} Gbp synthetic index ({args.species}x{args.strains}x{args.genome_len/1e6:g} Mbp), " +
-                               (f"{args.reads} long reads (5-20 kbp, mean {total_bases/args.reads:.0f} bp) per step per GPU, -k {k}, inputs resident in HBM" if longmode else
-                                f"{args.reads} x {'2x' if paired else ''}{args.read_len} bp {'PE' if paired else 'SE'} reads per step per GPU, -k {k}, inputs resident in HBM"),
-                   "index_bp": int(info.n), "reads_per_step_per_gpu": args.reads, "read_len": args.read_len,
-                   "parallelism": f"reads sharded over {world} GPU(s), index replicated, no collective",
-                   "numa_node_of_rank0": numa},
-        "classified_fraction": classified / args.reads,
-        "stage_ms": {k: float(np.mean([getattr(s, k) for s in kstats])) for k in
-                     ("pack_ms", "search_ms", "adjust_ms", "rows_ms", "locate_ms", "tail_ms", "total_ms")},
-    }
-
-    out["config"]["timed_entry"] = ("cfr_classify_batch_resident_compact (20 + 12 bytes per read / match slot to the host)" if entry["compact"]
-                                    else "cfr_classify_batch_resident (40 + 24 bytes per read / match slot to the host)")
+    out["index_on_ranks"] = {"ranks": len(ranks_index), "mapped_bytes_min": min(r_[0] for r_ in ranks_index), "copied_bytes_max": max(r_[1] for r_ in ranks_index),
+                             "device_image_bytes": ranks_index[0][2],
+                             "every_rank_maps_the_file": all(r_[0] > 0 and r_[1] == 0 for r_ in ranks_index)}
+    out["classified_fraction"] = classified / args.reads
     out["other_result_layout"] = {"layout": other_is, "value": args.reads * world / (ms_other / 1e3), "unit": out["unit"], "ms_per_step": ms_other,
                                   "note": "the same step through the other entry (rank 0's own clock): the results are the same fields in the other widths"}
     out["with_device_sdust"] = {"value": args.reads / (ms_with_dust / 1e3), "unit": out["unit"], "ms_per_step": ms_with_dust,
@@ -1810,7 +1880,7 @@ def main():
                     out["other_configs"][wname] = strains_config(torch, capi, ora, args, device, wname)
                 except Exception as e:
                     out["other_configs"][wname] = {"error": repr(e)}
-            if not args.no_40gbp:
+            if args.with_40gbp and not args.no_40gbp:
                 # BASELINE configs[3] / configs[4] on ONE GPU: the 40 Gbp index (written once by the native writer, ~4 min) and this
                 # rank's share of the reads - 12.5 M x 150 bp per step, 312 500 long reads per step - each in a process of its own
                 for cfg in ("cfg4", "cfg5"):

@@ -21,7 +21,7 @@ def test_eight_ranks_share_one_gpu(tmp_path):
     t0 = time.time()
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--config", "cfg4", "--index-gbp", "1", "--reads", "1000000",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--full", "--config", "cfg4", "--index-gbp", "1", "--reads", "1000000",
                         "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-pmc", "--count-sample", "20000", "--cache", str(tmp_path / "cache")],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=900)
     assert r.returncode == 0, "\n".join(ln for ln in r.stderr.decode().splitlines() if "rror" in ln or "Traceback" in ln or "bench" in ln)[-4000:]

@@ -2,7 +2,8 @@
 export CFR_DEBUG_ENV=1   # the gate behind which the library reads its CFR_* A/B switches
 # Stage timing of the drop-in command line on the bench sample (run on the GPU box; fills the bench cache first).
 mkdir -p gpurun_out
-python bench.py --steps 2 --warmup 1 --no-pmc --no-extra-configs > gpurun_out/cli_bench.json 2> gpurun_out/cli_bench.err
+mkdir -p /tmp/cfr_bench
+python bench.py --full --steps 2 --warmup 1 --no-pmc --no-extra-configs > /tmp/cfr_bench/cli_bench.json 2> /tmp/cfr_bench/cli_bench.err   # --full: the CPU leg writes sample_0.fa
 idx=$(ls /tmp/cfr_bench/*/idx.1.cfr 2>/dev/null | head -1); idx=${idx%.1.cfr}
 fa=$(ls /tmp/cfr_bench/*/sample_0.fa 2>/dev/null | head -1)
 out=gpurun_out/cli_timing.txt
@@ -39,7 +40,7 @@ if [ -x oracle/_ref/centrifuger ]; then
   md5sum /tmp/ref_gz.tsv /tmp/own_gz.tsv | tee -a $out
 fi
 # ---- pairs: 10 M pairs (-1/-2, -k 5) and the same as one interleaved file; plain files are cut at equal record numbers and parsed in pieces
-python bench.py --mode pe --steps 1 --warmup 1 --no-pmc --no-extra-configs > gpurun_out/cli_bench_pe.json 2> gpurun_out/cli_bench_pe.err
+python bench.py --full --mode pe --steps 1 --warmup 1 --no-pmc --no-extra-configs > /tmp/cfr_bench/cli_bench_pe.json 2> /tmp/cfr_bench/cli_bench_pe.err
 f1=$(ls /tmp/cfr_bench/*/sample_0.fa 2>/dev/null | head -1); f2=${f1%.fa}_2.fa
 if [ -f "$f2" ]; then
   for i in 1 2 3 4 5; do cat $f1; done > /tmp/big10m_1.fa

@@ -5,7 +5,8 @@
 export CFR_DEBUG_ENV=1
 M=${1:-100}
 mkdir -p gpurun_out
-python bench.py --steps 2 --warmup 1 --no-pmc --no-extra-configs --no-40gbp > gpurun_out/clifq_bench.json 2> gpurun_out/clifq_bench.err
+mkdir -p /tmp/cfr_bench
+python bench.py --full --steps 2 --warmup 1 --no-pmc --no-extra-configs --no-40gbp > /tmp/cfr_bench/clifq_bench.json 2> /tmp/cfr_bench/clifq_bench.err   # --full: the CPU leg writes sample_0.fa
 idx=$(ls /tmp/cfr_bench/*/idx.1.cfr 2>/dev/null | head -1); idx=${idx%.1.cfr}
 fa=$(ls /tmp/cfr_bench/*/sample_0.fa 2>/dev/null | head -1)
 out=gpurun_out/cli_timing_fastq.txt

@@ -18,7 +18,7 @@ cp centrifuger_amd/libcfr_hip.so /tmp/shipped.so
 for v in nt nt2; do
   cp tools/dbg/libcfr_hip_$v.so centrifuger_amd/libcfr_hip.so
   echo -n "gathers non-temporal ($v: 1 = all four slots, 2 = the table gather only) | cfg2: "; run
-  echo -n "   the same with PMC (value, requests/read, frac): "; python bench.py --no-cpu-baseline --no-extra-configs --steps 5 --warmup 2 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['value'], r.get('fabric_read_requests_per_read'), r.get('frac'), r.get('kernel_ms_alone'))"
+  echo -n "   the same with PMC (value, requests/read, frac): "; python bench.py --full --no-cpu-baseline --no-extra-configs --steps 5 --warmup 2 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['value'], r.get('fabric_read_requests_per_read'), r.get('frac'), r.get('kernel_ms_alone'))"
 done
 cp /tmp/shipped.so centrifuger_amd/libcfr_hip.so
-echo -n "shipped with PMC (value, requests/read, frac, alone ms): "; python bench.py --no-cpu-baseline --no-extra-configs --steps 5 --warmup 2 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['value'], r.get('fabric_read_requests_per_read'), r.get('frac'), r.get('kernel_ms_alone'))"
+echo -n "shipped with PMC (value, requests/read, frac, alone ms): "; python bench.py --full --no-cpu-baseline --no-extra-configs --steps 5 --warmup 2 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['value'], r.get('fabric_read_requests_per_read'), r.get('frac'), r.get('kernel_ms_alone'))"

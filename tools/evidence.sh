@@ -14,7 +14,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$ROOT/gpurun_out
 mkdir -p $O
 cd $ROOT
-CFR_BENCH_DETAIL=$O/${TAG}_bench_detail.json python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.log      # the compact line; the full object beside it
+CFR_BENCH_DETAIL=$O/${TAG}_bench_detail.json python bench.py --full --with-40gbp > $O/${TAG}_bench.json 2> $O/${TAG}_bench.log      # the compact line; the full object beside it
 # kernel trace of the plain entry alone: warm-up + timed steps and nothing else in the process, so that every dispatch divides by the steps
 ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats -d $O/${TAG}_trace -- python $ROOT/bench.py --inner --no-cpu-baseline --no-pmc --no-extra-configs --steps 10 --warmup 2 > $O/${TAG}_trace.json 2> $O/${TAG}_trace.log )
 db=$(find $O/${TAG}_trace -name "*.db" | head -1)
@@ -41,9 +41,9 @@ CFR_SUBBATCH=2000000 CFR_TAPER_FLOOR=0 tools/pmc_passes.sh $O/${TAG}_pmc --no-pm
 python tools/pmc_summary.py $O/${TAG}_pmc > $O/${TAG}_pmc_summary.txt 2>> $O/${TAG}_pmc.log
 python tools/pmc_latest.py $O/${TAG}_pmc $TAG $O/${TAG}_pmc_latest.json >> $O/${TAG}_pmc.log 2>&1
 rm -rf $O/${TAG}_pmc/pmc*/
-CFR_BENCH_SHARE_GPU=1 CFR_BENCH_DETAIL=$O/${TAG}_bench_2ranks_detail.json python bench.py --gpus 2 --steps 3 --no-cpu-baseline 2> $O/${TAG}_bench_2ranks.log | grep '^{"metric"' > $O/${TAG}_bench_2ranks.json   # (gloo prints its own lines on stdout)
+CFR_BENCH_SHARE_GPU=1 CFR_BENCH_DETAIL=$O/${TAG}_bench_2ranks_detail.json python bench.py --full --gpus 2 --steps 3 --no-cpu-baseline 2> $O/${TAG}_bench_2ranks.log | grep '^{"metric"' > $O/${TAG}_bench_2ranks.json   # (gloo prints its own lines on stdout)
 if [ -n "$BIG" ]; then
-  CFR_BENCH_DETAIL=$O/${TAG}_bench_8gbp_detail.json python bench.py --index-gbp 8 --steps 3 --cpu-sample 500000 > $O/${TAG}_bench_8gbp.json 2> $O/${TAG}_bench_8gbp.log
+  CFR_BENCH_DETAIL=$O/${TAG}_bench_8gbp_detail.json python bench.py --full --index-gbp 8 --steps 3 --cpu-sample 500000 > $O/${TAG}_bench_8gbp.json 2> $O/${TAG}_bench_8gbp.log
 fi
 python - <<PY
 import json

@@ -2,7 +2,7 @@
 # the many-strain workload (25 species x 20 strains 0.1 % apart): kernel times + search phase profile
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=${1:-$ROOT/gpurun_out/strain}; mkdir -p "$OUT"; OUT=$(cd "$OUT" && pwd); shift
-ARGS="--species 25 --strains 20 --genome-len 2000000 --divergence-step 0.001 --no-cpu-baseline --no-pmc --no-extra-configs --steps 3 --warmup 1"
+ARGS="--full --species 25 --strains 20 --genome-len 2000000 --divergence-step 0.001 --no-cpu-baseline --no-pmc --no-extra-configs --steps 3 --warmup 1"
 cd /tmp && export TMPDIR=/tmp
 rm -rf $OUT/trace
 env "$@" rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- python $ROOT/bench.py $ARGS > $OUT/bench.json 2> $OUT/bench.log
