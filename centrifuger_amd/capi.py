@@ -93,6 +93,8 @@ EXPORTS = [
     "cfr_format_tsv", "cfr_tsv_header", "cfr_host_alloc", "cfr_host_free",
     "cfr_classify_batch_submit", "cfr_classify_batch_wait", "cfr_compact_wide_reads", "cfr_index_digest", "cfr_index_mapped_bytes", "cfr_pack_reads", "cfr_classify_batch_packed",
     "cfr_classify_batch_expanded", "cfr_classify_from_hits_expanded", "cfr_format_tsv_expanded", "cfr_tsv_header_expanded",
+    "cfr_merge_pairs", "cfr_merge_pairs_device", "cfr_device_index_set_merge", "cfr_classify_batch_merged",
+    "cfr_classify_batch_resident_merged", "cfr_last_merge_ms",
 ]
 
 _lib = None
@@ -344,6 +346,52 @@ class DeviceIndex:
         offsets = _u64(offsets)
         _check(lib().cfr_dust_mask_device(self._d, _p(bases), _p(offsets), C.c_size_t(len(offsets) - 1)))
 
+    def set_merge(self, on: bool):
+        """--merge-readpair: classify_merged / classify_resident_merged merge overlapping pairs in HBM first (nucleotide indexes)."""
+        _check(lib().cfr_device_index_set_merge(self._d, C.c_int(1 if on else 0)))
+
+    def merge_pairs(self, bases1, offsets1, bases2, offsets2, qual1=None, qual2=None):
+        """The device merge kernels alone (cfr_merge_pairs_device), host arrays in and out: see merge_pairs()."""
+        return _merge_pairs(lambda *a: lib().cfr_merge_pairs_device(self._d, *a), bases1, offsets1, bases2, offsets2, qual1, qual2, None)
+
+    def classify_merged(self, bases1, offsets1, bases2=None, offsets2=None, qual1=None, qual2=None):
+        """cfr_classify_batch_merged -> (results, matches, merge_kind)"""
+        bases1, offsets1, bases2, offsets2, qual1, qual2 = _u8(bases1), _u64(offsets1), _u8(bases2), _u64(offsets2), _u8(qual1), _u8(qual2)
+        n = len(offsets1) - 1
+        results = np.zeros(n, dtype=RESULT_DTYPE)
+        kind = np.zeros(n, dtype=np.int32)
+        cap = max(16, max(1, self.index.params.max_result) * n)
+        while True:
+            matches = np.zeros(cap, dtype=MATCH_DTYPE)
+            nm = C.c_size_t(0)
+            st = lib().cfr_classify_batch_merged(self._d, _p(bases1), _p(offsets1), _p(qual1), _p(bases2), _p(offsets2), _p(qual2), C.c_size_t(n),
+                                                 _p(results), _p(matches), C.c_size_t(cap), C.byref(nm), _p(kind))
+            if st == CFR_ERR_CAPACITY:
+                cap = int(nm.value) + 16
+                continue
+            _check(st)
+            return results, matches[:nm.value], kind
+
+    def classify_resident_merged(self, d_bases1: int, d_offsets1: int, n: int, total1: int, d_bases2: int = 0, d_offsets2: int = 0,
+                                 total2: int = 0, d_qual1: int = 0, d_qual2: int = 0, results=None, matches=None):
+        """cfr_classify_batch_resident_merged: device pointers in (ints, qualities included) -> (results, matches, merge_kind)"""
+        if results is None:
+            results = np.zeros(n, dtype=RESULT_DTYPE)
+        if matches is None:
+            matches = np.zeros(max(16, max(1, self.index.params.max_result) * n), dtype=MATCH_DTYPE)
+        kind = np.zeros(n, dtype=np.int32)
+        nm = C.c_size_t(0)
+        _check(lib().cfr_classify_batch_resident_merged(self._d, C.c_void_p(d_bases1), C.c_void_p(d_offsets1), C.c_void_p(d_qual1 or None),
+                                                        C.c_void_p(d_bases2 or None), C.c_void_p(d_offsets2 or None), C.c_void_p(d_qual2 or None),
+                                                        C.c_size_t(n), C.c_uint64(total1), C.c_uint64(total2), _p(results), _p(matches),
+                                                        C.c_size_t(len(matches)), C.byref(nm), _p(kind)))
+        return results, matches[:nm.value], kind
+
+    def last_merge_ms(self) -> float:
+        ms = C.c_float(0)
+        _check(lib().cfr_last_merge_ms(self._d, C.byref(ms)))
+        return ms.value
+
     def close(self):
         if self._d:
             lib().cfr_device_index_destroy(self._d)
@@ -548,6 +596,31 @@ def dust_mask(bases, offsets, threads=1, literal=False):
     fn = lib().cfr_dust_mask_batch_literal if literal else lib().cfr_dust_mask_batch
     _check(fn(_p(bases), _p(offsets), C.c_size_t(len(offsets) - 1), C.c_int(threads)))
     return bases
+
+
+def _merge_pairs(call, bases1, offsets1, bases2, offsets2, qual1, qual2, threads):
+    bases1, offsets1, bases2, offsets2, qual1, qual2 = _u8(bases1), _u64(offsets1), _u8(bases2), _u64(offsets2), _u8(qual1), _u8(qual2)
+    n = len(offsets1) - 1
+    t1, t2 = int(offsets1[n]), int(offsets2[n])
+    ob1, ob2 = np.zeros(t1 + t2 + 1, dtype=np.uint8), np.zeros(t2 + 1, dtype=np.uint8)
+    oq1 = np.zeros(t1 + t2 + 1, dtype=np.uint8) if qual1 is not None else None
+    oq2 = np.zeros(t2 + 1, dtype=np.uint8) if qual1 is not None else None
+    oo1, oo2 = np.zeros(n + 1, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint64)
+    kind, overlap, offset = (np.zeros(n, dtype=np.int32) for _ in range(3))
+    args = [_p(bases1), _p(offsets1), _p(qual1), _p(bases2), _p(offsets2), _p(qual2), C.c_size_t(n)]
+    if threads is not None:
+        args.append(C.c_int(threads))
+    _check(call(*args, _p(ob1), _p(oo1), _p(oq1), _p(ob2), _p(oo2), _p(oq2), _p(kind), _p(overlap), _p(offset)))
+    m1, m2 = int(oo1[n]), int(oo2[n])
+    return {"bases1": ob1[:m1], "offsets1": oo1, "qual1": None if oq1 is None else oq1[:m1],
+            "bases2": ob2[:m2], "offsets2": oo2, "qual2": None if oq2 is None else oq2[:m2],
+            "kind": kind, "overlap": overlap, "offset": offset}
+
+
+def merge_pairs(bases1, offsets1, bases2, offsets2, qual1=None, qual2=None, threads=1):
+    """cfr_merge_pairs (ReadPairMerger::Merge per pair, on the host): dict of the new reads (merged pair: read 1 = the merged read,
+    read 2 = empty), their qualities when given, and kind / overlap / offset per pair."""
+    return _merge_pairs(lib().cfr_merge_pairs, bases1, offsets1, bases2, offsets2, qual1, qual2, threads)
 
 
 def pack_reads(bases, threads=1, out=None):

@@ -370,6 +370,7 @@ cfr_status cfr_classify_batch_packed(cfr_dev_index *d, const uint64_t *packed1, 
   if (!d || (n && (!packed1 || !offsets1 || !results))) return bad_arg("cfr_classify_batch_packed: null argument");
   if ((packed2 == nullptr) != (offsets2 == nullptr)) return bad_arg("cfr_classify_batch_packed: packed2/offsets2 must both be given");
   if (d->d->host().prot.enabled) return bad_arg("cfr_classify_batch_packed: a protein index needs the characters themselves (DnaToAa tells non-symbols apart): use cfr_classify_batch");
+  if (d->d->merge()) return bad_arg("cfr_classify_batch_packed: --merge-readpair is switched on and the packed form cannot tell 'N' from other bytes (ReadPairMerger compares them): use cfr_classify_batch_merged");
   CFR_ENTER(d, "cfr_classify_batch_packed");
   return guarded([&]() -> cfr_status {
     d->d->classify_host_packed(packed1, offsets1, packed2, offsets2, n, results, matches, match_cap, n_matches);
@@ -548,6 +549,142 @@ cfr_status cfr_dust_mask_device(cfr_dev_index *d, uint8_t *bases, const uint64_t
     d->d->dust_mask_host(bases, offsets, n);
     return CFR_OK;
   });
+}
+
+// ---- --merge-readpair ----
+static cfr_status merge_args(const char *who, const void *bases1, const void *offsets1, const void *qual1, const void *bases2, const void *offsets2,
+                             const void *qual2, size_t n) {
+  if (n && (!bases1 || !offsets1)) { g_err = std::string(who) + ": null argument"; return CFR_ERR_ARG; }
+  if ((bases2 == nullptr) != (offsets2 == nullptr)) { g_err = std::string(who) + ": bases2/offsets2 must both be given"; return CFR_ERR_ARG; }
+  if (bases2 && (qual1 == nullptr) != (qual2 == nullptr)) {
+    g_err = std::string(who) + ": qualities for both mates or for neither (ReadPairMerger::Merge reads both once one is given)";
+    return CFR_ERR_ARG;
+  }
+  return CFR_OK;
+}
+
+cfr_status cfr_merge_pairs(const uint8_t *bases1, const uint64_t *offsets1, const char *qual1, const uint8_t *bases2, const uint64_t *offsets2,
+                           const char *qual2, size_t n, int threads, uint8_t *out_bases1, uint64_t *out_offsets1, char *out_qual1,
+                           uint8_t *out_bases2, uint64_t *out_offsets2, char *out_qual2, int32_t *kind, int32_t *overlap, int32_t *offset) {
+  if (!out_offsets1 || !out_offsets2 || (n && (!bases2 || !out_bases1 || !out_bases2))) return bad_arg("cfr_merge_pairs: null argument");
+  if (cfr_status st = merge_args("cfr_merge_pairs", bases1, offsets1, qual1, bases2, offsets2, qual2, n)) return st;
+  for (size_t i = 0; i < n; ++i)
+    if (offsets1[i + 1] - offsets1[i] > 0x7fffffffull || offsets2[i + 1] - offsets2[i] > 0x7fffffffull) return bad_arg("cfr_merge_pairs: a mate of 2^31 bases or more");
+  if (threads < 1) threads = 1;
+  if ((size_t)threads > n) threads = n ? (int)n : 1;
+  // a contiguous slice of pairs per thread: the merged reads of a slice are kept in the thread's buffer until the new offsets are known
+  std::vector<int32_t> kd(n, 0);
+  std::vector<uint64_t> at(n, 0);
+  std::vector<std::vector<uint8_t>> mb((size_t)threads);
+  std::vector<std::vector<int8_t>> mq((size_t)threads);
+  auto run = [&](const std::function<void(int)> &f) {
+    if (threads == 1) { f(0); return; }
+    std::vector<std::thread> th;
+    for (int t = 0; t < threads; ++t) th.emplace_back(f, t);
+    for (auto &x : th) x.join();
+  };
+  run([&](int tid) {
+    const size_t lo = n * (size_t)tid / (size_t)threads, hi = n * (size_t)(tid + 1) / (size_t)threads;
+    cfr::MergeScratch ws;
+    std::vector<uint8_t> rm;
+    std::vector<int8_t> qm;
+    for (size_t i = lo; i < hi; ++i) {
+      const uint64_t a1 = offsets1[i], a2 = offsets2[i];
+      const int l1 = (int)(offsets1[i + 1] - a1), l2 = (int)(offsets2[i + 1] - a2);
+      rm.resize((size_t)l1 + (size_t)l2 + 1);
+      if (qual1) qm.resize((size_t)l1 + (size_t)l2 + 1);
+      int mlen = 0, ov = -1, off = -1;
+      const int k = cfr::merge_pair(bases1 + a1, qual1 ? (const int8_t *)qual1 + a1 : nullptr, l1, bases2 + a2, qual2 ? (const int8_t *)qual2 + a2 : nullptr, l2,
+                                    rm.data(), qual1 ? qm.data() : nullptr, &mlen, &ov, &off, ws);
+      kd[i] = k;
+      if (kind) kind[i] = k;
+      if (overlap) overlap[i] = ov;
+      if (offset) offset[i] = off;
+      out_offsets1[i + 1] = k ? (uint64_t)mlen : (uint64_t)l1;       // lengths for now
+      out_offsets2[i + 1] = k ? 0 : (uint64_t)l2;
+      if (k) {
+        at[i] = mb[tid].size();
+        mb[tid].insert(mb[tid].end(), rm.begin(), rm.begin() + mlen);
+        if (qual1) mq[tid].insert(mq[tid].end(), qm.begin(), qm.begin() + mlen);
+      }
+    }
+  });
+  out_offsets1[0] = out_offsets2[0] = 0;
+  for (size_t i = 0; i < n; ++i) { out_offsets1[i + 1] += out_offsets1[i]; out_offsets2[i + 1] += out_offsets2[i]; }
+  run([&](int tid) {
+    const size_t lo = n * (size_t)tid / (size_t)threads, hi = n * (size_t)(tid + 1) / (size_t)threads;
+    for (size_t i = lo; i < hi; ++i) {
+      const uint64_t d1 = out_offsets1[i], m1 = out_offsets1[i + 1] - d1, d2 = out_offsets2[i], m2 = out_offsets2[i + 1] - d2;
+      if (kd[i]) {
+        if (m1) memcpy(out_bases1 + d1, mb[tid].data() + at[i], m1);
+        if (m1 && qual1 && out_qual1) memcpy(out_qual1 + d1, mq[tid].data() + at[i], m1);
+      } else {
+        if (m1) memcpy(out_bases1 + d1, bases1 + offsets1[i], m1);
+        if (m2) memcpy(out_bases2 + d2, bases2 + offsets2[i], m2);
+        if (qual1 && out_qual1 && m1) memcpy(out_qual1 + d1, qual1 + offsets1[i], m1);
+        if (qual2 && out_qual2 && m2) memcpy(out_qual2 + d2, qual2 + offsets2[i], m2);
+      }
+    }
+  });
+  return CFR_OK;
+}
+
+cfr_status cfr_merge_pairs_device(cfr_dev_index *d, const uint8_t *bases1, const uint64_t *offsets1, const char *qual1, const uint8_t *bases2,
+                                  const uint64_t *offsets2, const char *qual2, size_t n, uint8_t *out_bases1, uint64_t *out_offsets1,
+                                  char *out_qual1, uint8_t *out_bases2, uint64_t *out_offsets2, char *out_qual2, int32_t *kind, int32_t *overlap,
+                                  int32_t *offset) {
+  if (!d || !out_offsets1 || !out_offsets2 || (n && (!bases2 || !out_bases1 || !out_bases2))) return bad_arg("cfr_merge_pairs_device: null argument");
+  if (cfr_status st = merge_args("cfr_merge_pairs_device", bases1, offsets1, qual1, bases2, offsets2, qual2, n)) return st;
+  for (size_t i = 0; i < n; ++i)
+    if (offsets1[i + 1] - offsets1[i] > 0x7fffffffull || offsets2[i + 1] - offsets2[i] > 0x7fffffffull) return bad_arg("cfr_merge_pairs_device: a mate of 2^31 bases or more");
+  CFR_ENTER(d, "cfr_merge_pairs_device");
+  return guarded([&]() -> cfr_status {
+    d->d->merge_pairs_host(bases1, offsets1, (const int8_t *)qual1, bases2, offsets2, (const int8_t *)qual2, n, out_bases1, out_offsets1,
+                           (int8_t *)(qual1 ? out_qual1 : nullptr), out_bases2, out_offsets2, (int8_t *)(qual1 ? out_qual2 : nullptr), kind, overlap, offset);
+    return CFR_OK;
+  });
+}
+
+cfr_status cfr_device_index_set_merge(cfr_dev_index *d, int on) {
+  if (!d) return bad_arg("cfr_device_index_set_merge: null argument");
+  if (d->d->host().prot.enabled) return bad_arg("cfr_device_index_set_merge: a protein index searches the mates translated; a merged pair's empty mate is not covered there");
+  CFR_ENTER(d, "cfr_device_index_set_merge");
+  d->d->set_merge(on != 0);
+  return CFR_OK;
+}
+
+cfr_status cfr_classify_batch_merged(cfr_dev_index *d, const uint8_t *bases1, const uint64_t *offsets1, const char *qual1, const uint8_t *bases2,
+                                     const uint64_t *offsets2, const char *qual2, size_t n, cfr_result *results, cfr_match *matches,
+                                     size_t match_cap, size_t *n_matches, int32_t *merge_kind) {
+  if (!d || (n && !results)) return bad_arg("cfr_classify_batch_merged: null argument");
+  if (cfr_status st = merge_args("cfr_classify_batch_merged", bases1, offsets1, qual1, bases2, offsets2, qual2, n)) return st;
+  CFR_ENTER(d, "cfr_classify_batch_merged");
+  return guarded([&]() -> cfr_status {
+    d->d->classify_host_merged(bases1, offsets1, (const int8_t *)qual1, bases2, offsets2, (const int8_t *)qual2, n, results, matches, match_cap,
+                               n_matches, merge_kind);
+    return CFR_OK;
+  });
+}
+
+cfr_status cfr_classify_batch_resident_merged(cfr_dev_index *d, const void *d_bases1, const void *d_offsets1, const void *d_qual1,
+                                              const void *d_bases2, const void *d_offsets2, const void *d_qual2, size_t n,
+                                              uint64_t total_bases1, uint64_t total_bases2, cfr_result *results, cfr_match *matches,
+                                              size_t match_cap, size_t *n_matches, int32_t *merge_kind) {
+  if (!d || (n && !results)) return bad_arg("cfr_classify_batch_resident_merged: null argument");
+  if (cfr_status st = merge_args("cfr_classify_batch_resident_merged", d_bases1, d_offsets1, d_qual1, d_bases2, d_offsets2, d_qual2, n)) return st;
+  CFR_ENTER(d, "cfr_classify_batch_resident_merged");
+  return guarded([&]() -> cfr_status {
+    d->d->classify_device_merged((const uint8_t *)d_bases1, (const uint64_t *)d_offsets1, (const int8_t *)d_qual1, (const uint8_t *)d_bases2,
+                                 (const uint64_t *)d_offsets2, (const int8_t *)d_qual2, n, total_bases1, total_bases2, results, matches, match_cap,
+                                 n_matches, merge_kind);
+    return CFR_OK;
+  });
+}
+
+cfr_status cfr_last_merge_ms(const cfr_dev_index *d, float *ms) {
+  if (!d || !ms) return bad_arg("cfr_last_merge_ms: null argument");
+  *ms = d->d->last_merge_ms;
+  return CFR_OK;
 }
 
 const char *cfr_tsv_header(void) {   // ResultWriter::OutputHeader (ResultWriter.hpp:186-197), no barcode/UMI columns

@@ -5,9 +5,10 @@
 // --un/--cl read dumps, same stderr summary lines.  What the reference does with
 // pthread_create(ClassifyReads_Thread) per batch (CentrifugerClass.cpp:681-688) is one
 // cfr_classify_batch call per batch here; batches round-robin over the GPUs given by --gpu, output stays
-// in input order.  Additive options: --gpu LIST|all, --gpu-batch N, --gpu-throughput.
-// Options of the reference that are outside this build (barcode/UMI/read-format/sample-sheet/
-// merge-readpair) are rejected with a message instead of being silently ignored.
+// in input order.  --merge-readpair (CentrifugerClass.cpp:256-335) merges the pairs on the device inside
+// cfr_classify_batch_merged (on the host when --un / --cl need the reads).  Additive options: --gpu LIST|all,
+// --gpu-batch N, --gpu-throughput.  Options of the reference that are outside this build (barcode/UMI/
+// read-format/sample-sheet) are rejected with a message instead of being silently ignored.
 #include <fcntl.h>
 #include <getopt.h>
 #include <cerrno>
@@ -52,6 +53,7 @@ const char *kUsage =
     "\t--un STR: output unclassified reads to files with the prefix of <str>\n"
     "\t--cl STR: output classified reads to files with the prefix of <str>\n"
     "\t--no-dust: do not DUST-mask low-complexity regions of reads [mask]\n"
+    "\t--merge-readpair: merge overlapped paired-end reads and trim adapters [no merge]\n"
     "\t--min-hitlen INT: minimum length of partial hits [auto]\n"
     "\t--hitk-factor INT: resolve at most <int>*k entries for each hit [40; use 0 for no restriction]\n"
     "\t--consider-secondary STR: in the format INT,FLOAT consider the secondary hit if its hitlen>=INT,score>=FLOAT*best_score [2000,0.995]\n"
@@ -64,7 +66,7 @@ const char *kUsage =
     "\t-h: print this usage message\n"
     "\t-v: print the version information and quit\n";
 
-enum { OPT_UN = 1000, OPT_CL, OPT_NO_DUST, OPT_MIN_HITLEN, OPT_HITK, OPT_SECONDARY, OPT_GPU, OPT_GPU_BATCH, OPT_GPU_THROUGHPUT, OPT_GPU_FASTLOAD, OPT_GPU_BALANCED, OPT_PARSE_THREADS, OPT_EXPAND_TAXID, OPT_UNSUPPORTED };
+enum { OPT_UN = 1000, OPT_CL, OPT_NO_DUST, OPT_MIN_HITLEN, OPT_HITK, OPT_SECONDARY, OPT_GPU, OPT_GPU_BATCH, OPT_GPU_THROUGHPUT, OPT_GPU_FASTLOAD, OPT_GPU_BALANCED, OPT_PARSE_THREADS, OPT_EXPAND_TAXID, OPT_MERGE_READPAIR, OPT_UNSUPPORTED };
 
 void print_log(const char *fmt, ...) {   // Utils::PrintLog (compactds/Utils.hpp:369-381)
   char buffer[1024];
@@ -592,6 +594,11 @@ struct Batch {
   std::vector<uint8_t> has_qual, has_qual2;
   ByteBuf bases1, bases2;
   std::vector<uint64_t> offs1, offs2;
+  // --merge-readpair with --un / --cl: the reads after the host merge (what is masked and classified; the dumps take a merged pair's
+  // mates from bases1 / bases2, which stay as they were read)
+  std::vector<uint8_t> m_bases1, m_bases2;
+  std::vector<uint64_t> m_offs1, m_offs2;
+  std::vector<int32_t> merge_kind;
   std::vector<cfr_result> results;
   std::vector<cfr_match> matches;
   std::vector<cfr_span> spans;         // --expand-taxid: per match slot, its list in exp_ids
@@ -665,6 +672,7 @@ struct Options {
   int threads = 1;
   cfr_params params;
   bool dust = true;
+  bool merge = false;                  // --merge-readpair
   std::string un_prefix, cl_prefix;
   std::vector<int> gpus{0};
   bool all_gpus = false;
@@ -725,7 +733,7 @@ int main(int argc, char *argv[]) {
       {"gpu-batch", required_argument, 0, OPT_GPU_BATCH}, {"gpu-throughput", no_argument, 0, OPT_GPU_THROUGHPUT},
       {"gpu-fast-load", no_argument, 0, OPT_GPU_FASTLOAD}, {"gpu-balanced", no_argument, 0, OPT_GPU_BALANCED},
       {"parse-threads", required_argument, 0, OPT_PARSE_THREADS},
-      {"sample-sheet", required_argument, 0, OPT_UNSUPPORTED}, {"merge-readpair", no_argument, 0, OPT_UNSUPPORTED},
+      {"sample-sheet", required_argument, 0, OPT_UNSUPPORTED}, {"merge-readpair", no_argument, 0, OPT_MERGE_READPAIR},
       {"expand-taxid", no_argument, 0, OPT_EXPAND_TAXID}, {"read-format", required_argument, 0, OPT_UNSUPPORTED},
       {"barcode", required_argument, 0, OPT_UNSUPPORTED}, {"UMI", required_argument, 0, OPT_UNSUPPORTED},
       {"barcode-whitelist", required_argument, 0, OPT_UNSUPPORTED}, {"barcode-translate", required_argument, 0, OPT_UNSUPPORTED},
@@ -745,6 +753,7 @@ int main(int argc, char *argv[]) {
       case OPT_UN: opt.un_prefix = optarg; break;
       case OPT_CL: opt.cl_prefix = optarg; break;
       case OPT_NO_DUST: opt.dust = false; break;
+      case OPT_MERGE_READPAIR: opt.merge = true; break;                    // CentrifugerClass.cpp:445-447
       case OPT_EXPAND_TAXID: opt.params.output_expanded = 1; break;       // CentrifugerClass.cpp:453-455
       case OPT_MIN_HITLEN: opt.params.min_hit_len = atoi(optarg); break;
       case OPT_HITK: opt.params.max_result_per_hit_factor = atoi(optarg); break;
@@ -791,6 +800,10 @@ int main(int argc, char *argv[]) {
     if (opt.gpu_batch > by_k) opt.gpu_batch = by_k;
   }
   const bool paired = !opt.m1.empty() || !opt.inter.empty();
+  if (opt.merge && !paired) {          // (the reference calls ReadPairMerger::Merge with a null mate there and does not survive it, ReadPairMerger.hpp:135-141)
+    print_log("ERROR: option --merge-readpair needs paired-end reads (-1 / -2 or -i); with single-end reads it is not available in this build.");
+    return EXIT_FAILURE;
+  }
   if (opt.m1.size() != opt.m2.size()) { print_log("ERROR: -1 and -2 must be given the same number of times."); return EXIT_FAILURE; }
   if (opt.u.empty() && !paired) { print_log("Need to use -u/-1/-2/-i to specify input reads."); return EXIT_FAILURE; }
   if ((int)!opt.u.empty() + (int)!opt.m1.empty() + (int)!opt.inter.empty() > 1) {
@@ -918,7 +931,7 @@ int main(int argc, char *argv[]) {
 
   std::thread reader([&]() {
     const bool interleaved = !opt.inter.empty();
-    const bool keep_qual = !opt.un_prefix.empty() || !opt.cl_prefix.empty();
+    const bool keep_qual = !opt.un_prefix.empty() || !opt.cl_prefix.empty() || opt.merge;      // (ReadPairMerger reads the qualities)
     size_t seq_no = 0;
     std::atomic<size_t> bases_hint{0};
     auto fresh_batch = [&]() {
@@ -1147,8 +1160,30 @@ int main(int argc, char *argv[]) {
     fclose(f4);
   }
   if (protein) opt.dust = false;
-  const bool host_dust = opt.dust && (!opt.un_prefix.empty() || !opt.cl_prefix.empty());
-  WorkerPool dust_pool(host_dust ? opt.threads : 1), format_pool(opt.threads);
+  if (protein && opt.merge) {
+    print_log("ERROR: --merge-readpair is not available with a protein index in this build: a merged pair is searched as one read with an "
+              "empty mate, and the translated search of an empty mate is not verified.");
+    exit(EXIT_FAILURE);                // (like die_status: the reader thread is already at work)
+  }
+  const bool dumps = !opt.un_prefix.empty() || !opt.cl_prefix.empty();
+  const bool host_dust = opt.dust && dumps;
+  // the dumps need to know which pairs merged before the masking: merge, then SDUST, on the host.  (--expand-taxid has its own classify
+  // entry, which takes reads that are merged already)
+  const bool host_merge = opt.merge && (dumps || opt.params.output_expanded != 0);  // the qualities of a batch as cfr_merge_pairs / cfr_classify_batch_merged take them: laid out by the bases' offsets, or none at all
+  auto batch_quals = [](const Batch &b, const char *&q1, const char *&q2) {
+    size_t with = 0;
+    for (size_t i = 0; i < b.n; ++i) with += (b.has_qual[i] ? 1 : 0) + (b.has_qual2[i] ? 1 : 0);
+    q1 = q2 = nullptr;
+    if (with == 0) return;
+    bool same = with == 2 * b.n;
+    for (size_t i = 0; same && i <= b.n; ++i) same = b.q1_off[i] == b.offs1[i] && b.q2_off[i] == b.offs2[i];
+    if (!same) {
+      print_log("ERROR: --merge-readpair needs qualities for every read of both files (FASTQ, as long as the sequences) or for none (FASTA).");
+      exit(EXIT_FAILURE);
+    }
+    q1 = b.qual1.data(); q2 = b.qual2.data();
+  };
+  WorkerPool dust_pool(host_dust || host_merge ? opt.threads : 1), format_pool(opt.threads);
   std::thread duster([&]() {
     for (;;) {
       std::shared_ptr<Batch> b;
@@ -1160,12 +1195,25 @@ int main(int argc, char *argv[]) {
         pending.pop_front();
       }
       const auto ts = tick();
+      uint8_t *dust1 = b->bases1.data(), *dust2 = b->paired ? b->bases2.data() : nullptr;
+      const uint64_t *dust_o1 = b->offs1.data(), *dust_o2 = b->offs2.data();
+      if (host_merge && b->n) {         // CentrifugerClass.cpp:271-273: the merge comes first
+        const char *q1, *q2;
+        batch_quals(*b, q1, q2);
+        b->m_bases1.resize(b->offs1[b->n] + b->offs2[b->n] + 1); b->m_bases2.resize(b->offs2[b->n] + 1);
+        b->m_offs1.resize(b->n + 1); b->m_offs2.resize(b->n + 1); b->merge_kind.resize(b->n);
+        const cfr_status ms = cfr_merge_pairs(b->bases1.data(), b->offs1.data(), q1, b->bases2.data(), b->offs2.data(), q2, b->n, opt.threads,
+                                              b->m_bases1.data(), b->m_offs1.data(), nullptr, b->m_bases2.data(), b->m_offs2.data(), nullptr,
+                                              b->merge_kind.data(), nullptr, nullptr);
+        if (ms != CFR_OK) die_status("cfr_merge_pairs", ms);
+        dust1 = b->m_bases1.data(); dust2 = b->m_bases2.data(); dust_o1 = b->m_offs1.data(); dust_o2 = b->m_offs2.data();
+      }
       if (opt.dust && host_dust) {      // slices of the batch on the stage's own workers (offsets are absolute, so a slice is just an offset window)
         const int parts = (int)std::min<size_t>((size_t)dust_pool.size(), std::max<size_t>(1, b->n / 2048));
         dust_pool.run(parts, [&](int t) {
           const size_t lo = b->n * (size_t)t / (size_t)parts, hi = b->n * (size_t)(t + 1) / (size_t)parts;
-          cfr_dust_mask_batch(b->bases1.data(), b->offs1.data() + lo, hi - lo, 1);
-          if (b->paired) cfr_dust_mask_batch(b->bases2.data(), b->offs2.data() + lo, hi - lo, 1);
+          cfr_dust_mask_batch(dust1, dust_o1 + lo, hi - lo, 1);
+          if (b->paired) cfr_dust_mask_batch(dust2, dust_o2 + lo, hi - lo, 1);
         });
       }
       clk.add(T_DUST, ts);
@@ -1217,6 +1265,7 @@ int main(int argc, char *argv[]) {
     st = cfr_device_index_create_ex(idx, g, &dopt, &d);
     if (st != CFR_OK) die_status("creating the device index (this build has no CPU fallback)", st);
     if (opt.dust && !host_dust) cfr_device_index_set_dust(d, 1);
+    if (opt.merge && !host_merge && (st = cfr_device_index_set_merge(d, 1)) != CFR_OK) die_status("cfr_device_index_set_merge", st);
     devs.push_back(d);
   }
   clk.add(T_DEVICE, t0);
@@ -1239,18 +1288,27 @@ int main(int argc, char *argv[]) {
       b->results.resize(b->n);
       size_t cap = b->n * (size_t)(opt.params.max_result > 0 ? opt.params.max_result : 4) + 16, used = 0;
       size_t ids_cap = expand ? std::max<size_t>(b->exp_ids.size(), 4 * b->n + 16) : 0, ids_used = 0;
+      // the reads the device gets: the batch as it was read (and masked), or what the host merge made of it
+      const bool merged_here = host_merge && b->n;
+      const uint8_t *in1 = merged_here ? b->m_bases1.data() : b->bases1.data();
+      const uint8_t *in2 = !b->paired ? nullptr : merged_here ? b->m_bases2.data() : b->bases2.data();
+      const uint64_t *in_o1 = merged_here ? b->m_offs1.data() : b->offs1.data();
+      const uint64_t *in_o2 = !b->paired ? nullptr : merged_here ? b->m_offs2.data() : b->offs2.data();
+      const char *mq1 = nullptr, *mq2 = nullptr;
+      const bool device_merge = opt.merge && !host_merge && b->paired && b->n;
+      if (device_merge) batch_quals(*b, mq1, mq2);
       for (;;) {
         b->matches.resize(cap);
         cfr_status s;
         if (expand) {
           b->spans.resize(cap);
           b->exp_ids.resize(ids_cap);
-          s = cfr_classify_batch_expanded(dev, b->bases1.data(), b->offs1.data(), b->paired ? b->bases2.data() : nullptr,
-                                          b->paired ? b->offs2.data() : nullptr, b->n, b->results.data(), b->matches.data(), b->spans.data(), cap, &used,
+          s = cfr_classify_batch_expanded(dev, in1, in_o1, in2, in_o2, b->n, b->results.data(), b->matches.data(), b->spans.data(), cap, &used,
                                           b->exp_ids.data(), ids_cap, &ids_used);
-        } else
-        s = cfr_classify_batch(dev, b->bases1.data(), b->offs1.data(), b->paired ? b->bases2.data() : nullptr,
-                               b->paired ? b->offs2.data() : nullptr, b->n, b->results.data(), b->matches.data(), cap, &used);
+        } else if (device_merge)
+          s = cfr_classify_batch_merged(dev, in1, in_o1, mq1, in2, in_o2, mq2, b->n, b->results.data(), b->matches.data(), cap, &used, nullptr);
+        else
+        s = cfr_classify_batch(dev, in1, in_o1, in2, in_o2, b->n, b->results.data(), b->matches.data(), cap, &used);
         if (s == CFR_ERR_CAPACITY) { if (used > cap) cap = used + 16; if (ids_used > ids_cap) ids_cap = ids_used + 16; continue; }
         if (s != CFR_OK) die_status("cfr_classify_batch", s);
         break;
@@ -1330,11 +1388,17 @@ int main(int argc, char *argv[]) {
       const bool hit = b->results[i].n_match > 0;
       ReadDump *dump = hit ? (cl.fp[0] ? &cl : nullptr) : (un.fp[0] ? &un : nullptr);
       if (!dump) continue;
-      dump->put(0, b->id(i), b->bases1.data() + b->offs1[i], b->offs1[i + 1] - b->offs1[i],
+      // --merge-readpair: a merged pair is dumped as its original mates (only the merged read was masked, CentrifugerClass.cpp:304-315),
+      // every other pair as the masked mates (which the host merge left in its own buffers)
+      const bool from_merge = host_merge && !b->merge_kind[i];
+      const uint8_t *s1 = from_merge ? b->m_bases1.data() + b->m_offs1[i] : b->bases1.data() + b->offs1[i];
+      dump->put(0, b->id(i), s1, b->offs1[i + 1] - b->offs1[i],
                 b->has_qual[i] ? b->qual1.data() + b->q1_off[i] : nullptr, b->q1_off[i + 1] - b->q1_off[i]);
-      if (b->paired)
-        dump->put(1, b->id(i), b->bases2.data() + b->offs2[i], b->offs2[i + 1] - b->offs2[i],
+      if (b->paired) {
+        const uint8_t *s2 = from_merge ? b->m_bases2.data() + b->m_offs2[i] : b->bases2.data() + b->offs2[i];
+        dump->put(1, b->id(i), s2, b->offs2[i + 1] - b->offs2[i],
                   b->has_qual2[i] ? b->qual2.data() + b->q2_off[i] : nullptr, b->q2_off[i + 1] - b->q2_off[i]);
+      }
     }
     clk.add(T_WRITE, tw);
     std::lock_guard<std::mutex> lk(mu);

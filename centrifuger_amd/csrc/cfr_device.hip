@@ -38,7 +38,7 @@ inline unsigned grid_for(size_t n, int block = kBlock) { return (unsigned)((n + 
 
 enum Slot : size_t {
   S_CAP = 0, S_HITOFF, S_RAW, S_CHAINCNT, S_SCAN2, S_POOL_E, S_POOL_V, S_POOLCTL, S_POOLCTL1, S_FIN, S_FINCNT, S_FINROWS, S_FINOFF, S_HITS, S_ROWSPER, S_ROWOFF, S_ROWS,
-  S_ROWVALS, S_PACK1, S_PACK2, S_READROWS, S_READROWOFF, S_ENTRIES, S_RESULTS, S_MATCHES, S_RESULTS1, S_MATCHES1, S_SCAN, S_IN_B1, S_IN_O1, S_IN_B2, S_IN_O2, S_DUSTPOOL, S_DUSTPOOL2, S_DUSTTMP, S_DUSTTMP2, S_DUSTFLAG, S_DUSTFLAG2, S_HEAVY, S_HEAVYB, S_HEAVYB1, S_CAP1, S_HITOFF1, S_RAW1, S_CHAINCNT1, S_SCAN1, S_HEAVY1, S_CRES, S_CRES1, S_CMATCH, S_CMATCH1, S_WIDEIDX, S_WIDERES, S_WIDEMATCH, S_WIDECNT, S_PCODES1, S_PCODES2, S_CAPALL, S_HITALL, S_SCANALL, S_P0, S_P1, S_P2, S_P3, S_P4, S_P5, S_EXPPOOL, S_EXPCUR, S_SLOW, S_SLOW1, S_LIST, S_LIST1, S_LISTCTR, S_COUNT
+  S_ROWVALS, S_PACK1, S_PACK2, S_READROWS, S_READROWOFF, S_ENTRIES, S_RESULTS, S_MATCHES, S_RESULTS1, S_MATCHES1, S_SCAN, S_IN_B1, S_IN_O1, S_IN_B2, S_IN_O2, S_DUSTPOOL, S_DUSTPOOL2, S_DUSTTMP, S_DUSTTMP2, S_DUSTFLAG, S_DUSTFLAG2, S_HEAVY, S_HEAVYB, S_HEAVYB1, S_CAP1, S_HITOFF1, S_RAW1, S_CHAINCNT1, S_SCAN1, S_HEAVY1, S_CRES, S_CRES1, S_CMATCH, S_CMATCH1, S_WIDEIDX, S_WIDERES, S_WIDEMATCH, S_WIDECNT, S_PCODES1, S_PCODES2, S_CAPALL, S_HITALL, S_SCANALL, S_P0, S_P1, S_P2, S_P3, S_P4, S_P5, S_EXPPOOL, S_EXPCUR, S_SLOW, S_SLOW1, S_LIST, S_LIST1, S_LISTCTR, S_IN_Q1, S_IN_Q2, S_MRG_B1, S_MRG_B2, S_MRG_Q1, S_MRG_Q2, S_MRG_O1, S_MRG_O2, S_MRG_LEN1, S_MRG_LEN2, S_MRG_DEC, S_MRG_SCAN, S_COUNT
 };
 
 }  // namespace
@@ -713,6 +713,7 @@ void DeviceIndex::release() {            // idempotent: also the clean-up of a c
   for (auto &e : h2d_done_) drop_event(e);
   for (auto &e : copied_) drop_event(e);
   for (auto &e : search_done_) drop_event(e);
+  for (auto &e : merge_ev_) drop_event(e);
   auto drop_stream = [](hipStream_t &s) { if (s) (void)hipStreamDestroy(s); s = nullptr; };
   drop_stream(tail_stream_);
   drop_stream(search2_stream_);
@@ -1894,6 +1895,104 @@ void DeviceIndex::classify_host_packed(const uint64_t *p1, const uint64_t *o1, c
     HIP_CHECK(hipMemcpyAsync(d_o2, o2, (n + 1) * 8, hipMemcpyHostToDevice, stream_));
   }
   classify_device(d_b1, d_o1, d_b2, d_o2, n, t1, t2, results, matches, match_cap, match_extent);
+}
+
+// ------------------------------------------------------------------------------------ --merge-readpair
+// ReadPairMerger::Merge (the reference's pre-step in front of SDUST and Query, CentrifugerClass.cpp:256-335) on pairs that are
+// already in HBM, on the library's stream: decide per pair, scan the new lengths, write the new reads into buffers of the image.
+// The caller's buffers are not modified.  One 16-byte read-back (the new totals size everything behind it).
+DeviceIndex::Merged DeviceIndex::merge_on_device(const uint8_t *d_b1, const uint64_t *d_o1, const int8_t *d_q1, const uint8_t *d_b2,
+                                                 const uint64_t *d_o2, const int8_t *d_q2, size_t n, uint64_t total1, uint64_t total2,
+                                                 bool want_qual) {
+  if (!merge_ready_) {
+    int32_t thr[kMergeThrTable];
+    merge_threshold_table(thr);
+    HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_merge_thr), thr, sizeof(thr)));
+    for (auto &e : merge_ev_) HIP_CHECK(hipEventCreate(&e));
+    merge_ready_ = true;
+  }
+  int32_t *dec = (int32_t *)scratch(S_MRG_DEC, 3 * n * sizeof(int32_t));
+  uint64_t *len1 = (uint64_t *)scratch(S_MRG_LEN1, (n + 1) * 8), *len2 = (uint64_t *)scratch(S_MRG_LEN2, (n + 1) * 8);
+  uint64_t *no1 = (uint64_t *)scratch(S_MRG_O1, (n + 1) * 8), *no2 = (uint64_t *)scratch(S_MRG_O2, (n + 1) * 8);
+  uint8_t *ob1 = (uint8_t *)scratch(S_MRG_B1, total1 + total2 + 16), *ob2 = (uint8_t *)scratch(S_MRG_B2, total2 + 16);
+  int8_t *oq1 = nullptr, *oq2 = nullptr;
+  if (want_qual && d_q1) { oq1 = (int8_t *)scratch(S_MRG_Q1, total1 + total2 + 16); oq2 = (int8_t *)scratch(S_MRG_Q2, total2 + 16); }
+  const size_t tmp_bytes = scan_tmp_bytes(n);
+  void *tmp = scratch(S_MRG_SCAN, tmp_bytes);
+  const unsigned grid = std::min<unsigned>(grid_for(n, 4), (unsigned)(num_cus_ * 8));     // a wave per pair, eight blocks of four per CU
+  HIP_CHECK(hipEventRecord(merge_ev_[0], stream_));
+  HIP_CHECK(hipMemsetAsync(len1 + n, 0, 8, stream_));
+  HIP_CHECK(hipMemsetAsync(len2 + n, 0, 8, stream_));
+  k_merge_decide<<<grid, 256, 0, stream_>>>(d_b1, d_o1, d_b2, d_o2, n, dec, dec + n, dec + 2 * n, len1, len2);
+  exclusive_scan(tmp, tmp_bytes, len1, no1, n, stream_);
+  exclusive_scan(tmp, tmp_bytes, len2, no2, n, stream_);
+  k_merge_write<<<grid, 256, 0, stream_>>>(d_b1, d_o1, d_q1, d_b2, d_o2, d_q2, n, dec, dec + 2 * n, no1, no2, ob1, oq1, ob2, oq2);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(merge_ev_[1], stream_));
+  uint64_t *tot = (uint64_t *)pinned(16);
+  HIP_CHECK(hipMemcpyAsync(tot, no1 + n, 8, hipMemcpyDeviceToHost, stream_));
+  HIP_CHECK(hipMemcpyAsync(tot + 1, no2 + n, 8, hipMemcpyDeviceToHost, stream_));
+  HIP_CHECK(hipStreamSynchronize(stream_));
+  (void)hipEventElapsedTime(&last_merge_ms, merge_ev_[0], merge_ev_[1]);
+  return Merged{ob1, no1, ob2, no2, tot[0], tot[1], oq1, oq2, dec};
+}
+
+void DeviceIndex::classify_device_merged(const uint8_t *d_b1, const uint64_t *d_o1, const int8_t *d_q1, const uint8_t *d_b2, const uint64_t *d_o2,
+                                         const int8_t *d_q2, size_t n, uint64_t total1, uint64_t total2, cfr_result *results, cfr_match *matches,
+                                         size_t match_cap, size_t *match_extent, int32_t *kind) {
+  HIP_CHECK(hipSetDevice(device_));
+  last_merge_ms = 0.f;
+  if (kind && n) memset(kind, 0, n * sizeof(int32_t));
+  if (!merge_ || !d_b2 || n == 0 || view_.prot.enabled) {      // switched off, or single-end: the batch as it is
+    classify_device(d_b1, d_o1, d_b2, d_o2, n, total1, total2, results, matches, match_cap, match_extent);
+    return;
+  }
+  const Merged m = merge_on_device(d_b1, d_o1, d_q1, d_b2, d_o2, d_q2, n, total1, total2, false);
+  if (kind) HIP_CHECK(hipMemcpy(kind, m.dec, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  classify_device(m.b1, m.o1, m.b2, m.o2, n, m.t1, m.t2, results, matches, match_cap, match_extent);
+}
+
+void DeviceIndex::classify_host_merged(const uint8_t *b1, const uint64_t *o1, const int8_t *q1, const uint8_t *b2, const uint64_t *o2, const int8_t *q2,
+                                       size_t n, cfr_result *results, cfr_match *matches, size_t match_cap, size_t *match_extent, int32_t *kind) {
+  HIP_CHECK(hipSetDevice(device_));
+  if (!merge_ || !b2 || n == 0 || view_.prot.enabled) {
+    last_merge_ms = 0.f;
+    if (kind && n) memset(kind, 0, n * sizeof(int32_t));
+    classify_host(b1, o1, b2, o2, n, results, matches, match_cap, match_extent);
+    return;
+  }
+  // the merge needs both mates of every pair in HBM before the first search: the whole batch goes up front (no streamed upload)
+  const Staged st = stage_inputs(b1, o1, b2, o2, n);
+  int8_t *d_q1 = nullptr, *d_q2 = nullptr;
+  if (q1) {
+    d_q1 = (int8_t *)scratch(S_IN_Q1, st.t1 + 16);
+    d_q2 = (int8_t *)scratch(S_IN_Q2, st.t2 + 16);
+    if (st.t1) HIP_CHECK(hipMemcpyAsync(d_q1, q1, st.t1, hipMemcpyHostToDevice, stream_));
+    if (st.t2) HIP_CHECK(hipMemcpyAsync(d_q2, q2, st.t2, hipMemcpyHostToDevice, stream_));
+  }
+  classify_device_merged(st.b1, st.o1, d_q1, st.b2, st.o2, d_q2, n, st.t1, st.t2, results, matches, match_cap, match_extent, kind);
+}
+
+void DeviceIndex::merge_pairs_host(const uint8_t *b1, const uint64_t *o1, const int8_t *q1, const uint8_t *b2, const uint64_t *o2, const int8_t *q2,
+                                   size_t n, uint8_t *ob1, uint64_t *oo1, int8_t *oq1, uint8_t *ob2, uint64_t *oo2, int8_t *oq2, int32_t *kind,
+                                   int32_t *overlap, int32_t *offset) {
+  HIP_CHECK(hipSetDevice(device_));
+  if (n == 0) { oo1[0] = 0; oo2[0] = 0; return; }
+  const Staged st = stage_inputs(b1, o1, b2, o2, n);
+  int8_t *d_q1 = nullptr, *d_q2 = nullptr;
+  if (q1) {
+    d_q1 = (int8_t *)scratch(S_IN_Q1, st.t1 + 16);
+    d_q2 = (int8_t *)scratch(S_IN_Q2, st.t2 + 16);
+    if (st.t1) HIP_CHECK(hipMemcpyAsync(d_q1, q1, st.t1, hipMemcpyHostToDevice, stream_));
+    if (st.t2) HIP_CHECK(hipMemcpyAsync(d_q2, q2, st.t2, hipMemcpyHostToDevice, stream_));
+  }
+  const Merged m = merge_on_device(st.b1, st.o1, d_q1, st.b2, st.o2, d_q2, n, st.t1, st.t2, oq1 != nullptr);
+  auto down = [&](void *dst, const void *src, size_t bytes) { if (dst && bytes) HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream_)); };
+  down(ob1, m.b1, m.t1); down(ob2, m.b2, m.t2);
+  down(oo1, m.o1, (n + 1) * 8); down(oo2, m.o2, (n + 1) * 8);
+  if (m.q1) { down(oq1, m.q1, m.t1); down(oq2, m.q2, m.t2); }
+  down(kind, m.dec, n * 4); down(overlap, m.dec + n, n * 4); down(offset, m.dec + 2 * n, n * 4);
+  HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
 void *DeviceIndex::pinned(size_t bytes) {

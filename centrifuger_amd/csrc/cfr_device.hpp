@@ -193,7 +193,29 @@ class DeviceIndex {
   // host buffers in/out: the device scan as a stand-alone entry (parity probe of k_dust)
   void dust_mask_host(uint8_t *bases, const uint64_t *offs, size_t n);
 
+  // --merge-readpair (ReadPairMerger::Merge in front of SDUST and Query, CentrifugerClass.cpp:256-335): when switched on, the *_merged
+  // classify calls merge every pair whose mates overlap into read 1 (read 2 becomes empty) in HBM before anything else.  q1 / q2:
+  // the qualities (same offsets as the bases), both or neither.  kind: n entries on the host (0 none, 1 overlap, 2 read-through)
+  void set_merge(bool on) { merge_ = on; }
+  bool merge() const { return merge_; }
+  void classify_device_merged(const uint8_t *d_b1, const uint64_t *d_o1, const int8_t *d_q1, const uint8_t *d_b2, const uint64_t *d_o2,
+                              const int8_t *d_q2, size_t n, uint64_t total1, uint64_t total2, cfr_result *results, cfr_match *matches,
+                              size_t match_cap, size_t *match_extent, int32_t *kind);
+  void classify_host_merged(const uint8_t *b1, const uint64_t *o1, const int8_t *q1, const uint8_t *b2, const uint64_t *o2, const int8_t *q2,
+                            size_t n, cfr_result *results, cfr_match *matches, size_t match_cap, size_t *match_extent, int32_t *kind);
+  // host buffers in/out: the merge kernels as a stand-alone entry (parity probe of k_merge_decide / k_merge_write)
+  void merge_pairs_host(const uint8_t *b1, const uint64_t *o1, const int8_t *q1, const uint8_t *b2, const uint64_t *o2, const int8_t *q2, size_t n,
+                        uint8_t *ob1, uint64_t *oo1, int8_t *oq1, uint8_t *ob2, uint64_t *oo2, int8_t *oq2, int32_t *kind, int32_t *overlap,
+                        int32_t *offset);
+  float last_merge_ms = 0.f;            // device time of the merge pre-step of the last *_merged call (0 when it did not run)
+
  private:
+  struct Merged { const uint8_t *b1; const uint64_t *o1; const uint8_t *b2; const uint64_t *o2; uint64_t t1, t2;
+                  const int8_t *q1, *q2; const int32_t *dec; };                  // dec: kind[n], overlap[n], offset[n] on the device
+  Merged merge_on_device(const uint8_t *d_b1, const uint64_t *d_o1, const int8_t *d_q1, const uint8_t *d_b2, const uint64_t *d_o2,
+                         const int8_t *d_q2, size_t n, uint64_t total1, uint64_t total2, bool want_qual);
+  bool merge_ = false, merge_ready_ = false;
+  hipEvent_t merge_ev_[2] = {};
   void init(const HostIndex &h, const cfr_device_options &opt);
   void release();
   void *temp_alloc(size_t bytes);

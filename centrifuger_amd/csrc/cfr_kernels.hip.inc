@@ -4670,4 +4670,216 @@ __global__ __launch_bounds__(256, STAGE == 1 && !WIDE && CPR == 2 ? CFR_FIRST_MI
   }
 }
 
+// ------------------------------------------------------------------------------------ --merge-readpair
+// ReadPairMerger::Merge (ReadPairMerger.hpp:132-233; host twin: cfr_merge.cpp) for pairs that are already in HBM: k_merge_decide
+// finds kind / overlap / offset and the new lengths of every pair, a scan turns the lengths into offsets, k_merge_write writes the
+// new reads (merged pair: read 1 = the merged read, read 2 = empty; the others as they are).
+//
+// One wave per pair, lanes = candidate offsets j of IsMateOverlap (ReadPairMerger.hpp:20-50).  Without the reference's early exit:
+// with K = min(flen - j, slen) compared positions and mism mismatches among them, its running test
+// matchCnt + (flen - (j + k) - 1) < T is (flen - j) - mism_k < T with mism_k non-decreasing in k, so offset j passes iff
+// (flen - j) - mism >= T(flen - j) (always when K == 0), and overlapSize = K.  One side of every compare is the complemented mate
+// (A C G T N only), so a byte of the raw side matches only if it is one of those five: both sides as three bit planes of the codes
+// A 0, C 1, G 2, T 3, N 4, anything else 5 (raw side only), mism = popcount of (x0^y0)|(x1^y1)|(x2^y2) over the first sequence's
+// planes funnel-shifted by j.  Mates of up to kMergeFastLen bases keep their planes in LDS; longer ones are compared byte by byte
+// from memory (correct for any length below 2^31, not fast).
+constexpr int kMergeFastLen = 512, kMergeWords = kMergeFastLen / 64;
+__constant__ int32_t c_merge_thr[100];      // int(L * similarityThreshold) for L < 100, filled by the host twin's own expression (merge_threshold_table)
+
+__device__ __forceinline__ uint32_t merge_code_raw(uint8_t c) {
+  return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : c == 'N' ? 4u : 5u;
+}
+__device__ __forceinline__ uint32_t merge_code_comp(uint8_t c) {      // code of _compChar[c]
+  return c == 'A' ? 3u : c == 'C' ? 2u : c == 'G' ? 1u : c == 'T' ? 0u : 4u;
+}
+__device__ __forceinline__ uint8_t merge_comp_char(uint8_t c) {       // _compChar (ReadPairMerger.hpp:105-111)
+  return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : 'N';
+}
+__device__ __forceinline__ int merge_threshold(int L) {               // from 100 on: one IEEE double multiply (nothing to contract it with)
+  return L < 100 ? c_merge_thr[L] : (int)((double)L * 0.85);
+}
+
+// IsMateOverlap's offset loop on the planes: F = first sequence (flen), S = second (slen).  cnt = offsets that pass, last = the largest of them
+__device__ __forceinline__ void merge_pass_planes(const uint64_t (*F)[kMergeWords + 1], const uint64_t (*S)[kMergeWords + 1], int flen, int slen,
+                                                  int min_overlap, uint32_t lane, int &cnt, int &last) {
+  cnt = 0; last = -1;
+  const int nj = flen - min_overlap;
+  for (int j0 = 0; j0 < nj; j0 += 64) {
+    const int j = j0 + (int)lane;
+    bool ok = false;
+    if (j < nj) {
+      const int L = flen - j, K = L < slen ? L : slen;
+      const int q = j >> 6, sh = j & 63;
+      int mism = 0;
+      for (int w = 0; w * 64 < K; ++w) {
+        uint64_t d = 0;
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+          const uint64_t lo = F[b][q + w], hi = F[b][q + w + 1];
+          const uint64_t x = sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
+          d |= x ^ S[b][w];
+        }
+        const int rem = K - w * 64;
+        if (rem < 64) d &= (1ull << rem) - 1ull;
+        mism += __popcll(d);
+      }
+      ok = K == 0 || L - mism >= merge_threshold(L);
+    }
+    const unsigned long long m = __ballot(ok);
+    if (m) { cnt += __popcll(m); last = j0 + 63 - __clzll((long long)m); }
+  }
+}
+
+// the same loop on the bytes themselves (long mates).  RC_FIRST: the first sequence is the reverse complement of r2 (the
+// read-through pass), else r1 (the plain pass); the other one is the second sequence
+template <bool RC_FIRST>
+__device__ __forceinline__ void merge_pass_bytes(const uint8_t *r1, int len1, const uint8_t *r2, int len2, int min_overlap, uint32_t lane,
+                                                 int &cnt, int &last) {
+  cnt = 0; last = -1;
+  const int flen = RC_FIRST ? len2 : len1, slen = RC_FIRST ? len1 : len2;
+  const int nj = flen - min_overlap;
+  for (int j0 = 0; j0 < nj; j0 += 64) {
+    bool ok = false;
+    if ((int)lane < nj - j0) {            // (j0 + lane may not fit an int for the lanes past the end)
+      const int j = j0 + (int)lane;
+      const int L = flen - j, K = L < slen ? L : slen;
+      const int T = merge_threshold(L);
+      int mism = 0;
+      for (int k = 0; k < K && L - mism >= T; ++k) {
+        const uint8_t a = RC_FIRST ? merge_comp_char(r2[len2 - 1 - (j + k)]) : r1[j + k];
+        const uint8_t c = RC_FIRST ? r1[k] : merge_comp_char(r2[len2 - 1 - k]);
+        mism += a != c;
+      }
+      ok = K == 0 || L - mism >= T;
+    }
+    const unsigned long long m = __ballot(ok);
+    if (m) { cnt += __popcll(m); last = j0 + 63 - __clzll((long long)m); }
+    if (nj - j0 <= 64) break;
+  }
+}
+
+// kind: 0 no merge, 1 overlap, 2 read-through; overlap / offset: what ReadPairMerger::Merge leaves in overlapSize / offset (for kind 0:
+// -1 and the last offset that passed, or -1); len1 / len2: lengths of the pair's reads after the merge (entry n of both is left alone:
+// the caller zeroes it for the scan)
+__global__ __launch_bounds__(256) void k_merge_decide(const uint8_t *bases1, const uint64_t *offs1, const uint8_t *bases2, const uint64_t *offs2, size_t n,
+                                                      int32_t *kind, int32_t *overlap, int32_t *offset, uint64_t *len1_out, uint64_t *len2_out) {
+  __shared__ uint64_t s_planes[4][2][3][kMergeWords + 1];      // per wave: [0] r1 as it is, [1] the reverse complement of r2
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  uint64_t (*P1)[kMergeWords + 1] = s_planes[wv][0];
+  uint64_t (*P2)[kMergeWords + 1] = s_planes[wv][1];
+  auto wave_sync = [] {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  };
+  for (size_t pair = (size_t)blockIdx.x * 4 + wv; pair < n; pair += (size_t)gridDim.x * 4) {
+    const uint64_t a1 = offs1[pair], a2 = offs2[pair];
+    const uint8_t *r1 = bases1 + a1, *r2 = bases2 + a2;
+    const int len1 = (int)(offs1[pair + 1] - a1), len2 = (int)(offs2[pair + 1] - a2);
+    const int64_t tenth = ((int64_t)len1 + (int64_t)len2) / 10;
+    const int min_overlap = tenth > 31 ? 31 : (int)tenth;
+    const bool fast = len1 <= kMergeFastLen && len2 <= kMergeFastLen;
+    if (fast) {
+      const int nw = ((len1 > len2 ? len1 : len2) + 63) >> 6;          // words in use; one more (zero) word for the funnel shift
+      for (int w = 0; w <= nw; ++w) {
+        const int p = w * 64 + (int)lane;
+        const uint32_t c1 = p < len1 ? merge_code_raw(r1[p]) : 0u;
+        const uint32_t c2 = p < len2 ? merge_code_comp(r2[len2 - 1 - p]) : 0u;
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+          const unsigned long long m1 = __ballot((c1 >> b) & 1u), m2 = __ballot((c2 >> b) & 1u);
+          if (lane == (uint32_t)b) { P1[b][w] = m1; P2[b][w] = m2; }
+        }
+      }
+      wave_sync();
+    }
+    int cnt = 0, last = -1, k = 0, ov = -1, off = -1;
+    // read through: first = rc(r2), second = r1, no tandem check
+    if (fast) merge_pass_planes(P2, P1, len2, len1, min_overlap, lane, cnt, last);
+    else merge_pass_bytes<true>(r1, len1, r2, len2, min_overlap, lane, cnt, last);
+    if (last >= 0) off = last;
+    if (cnt == 1) {
+      k = 2;
+      ov = len2 - last < len1 ? len2 - last : len1;
+    } else {
+      // plain overlap: first = r1, second = rc(r2)
+      if (fast) merge_pass_planes(P1, P2, len1, len2, min_overlap, lane, cnt, last);
+      else merge_pass_bytes<false>(r1, len1, r2, len2, min_overlap, lane, cnt, last);
+      if (last >= 0) off = last;
+      if (cnt == 1) {
+        const int K = len1 - last < len2 ? len1 - last : len2;
+        bool tandem = false;
+        if (K <= 2 * min_overlap) {       // K <= 62: lane i tests the repeat size i (ReadPairMerger.hpp:57-79): every full block equals the first
+          bool t = false;
+          const int i = (int)lane;
+          if (i >= 1 && i <= K / 2) {
+            t = true;
+            const int m = (K / i) * i;
+            for (int x = i; x < m; ++x)
+              if (merge_comp_char(r2[len2 - 1 - x]) != merge_comp_char(r2[len2 - 1 - (x - i)])) { t = false; break; }
+          }
+          tandem = __ballot(t) != 0ull;
+        }
+        if (!tandem) { k = 1; ov = K; }
+      }
+    }
+    if (lane == 0) {
+      kind[pair] = k; overlap[pair] = ov; offset[pair] = off;
+      len1_out[pair] = k == 2 ? (uint64_t)ov : k == 1 ? (uint64_t)off + (uint64_t)len2 : (uint64_t)len1;
+      len2_out[pair] = k ? 0ull : (uint64_t)len2;
+    }
+    if (fast) wave_sync();                // the planes are overwritten by the next pair
+  }
+}
+
+// The reads after the merge, one wave per pair, lanes along the bytes.  q1 / q2: the qualities (both or neither: without them the
+// quality terms of ReadPairMerger.hpp:171-185, 211 drop out as its q1 != NULL tests do), compared as signed char; oq1 / oq2: the
+// qualities of the new reads when the caller wants them (the parity probe), else nullptr
+__global__ __launch_bounds__(256) void k_merge_write(const uint8_t *bases1, const uint64_t *offs1, const int8_t *q1, const uint8_t *bases2, const uint64_t *offs2,
+                                                     const int8_t *q2, size_t n, const int32_t *kind, const int32_t *offset, const uint64_t *noffs1,
+                                                     const uint64_t *noffs2, uint8_t *ob1, int8_t *oq1, uint8_t *ob2, int8_t *oq2) {
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  for (size_t pair = (size_t)blockIdx.x * 4 + wv; pair < n; pair += (size_t)gridDim.x * 4) {
+    const uint64_t a1 = offs1[pair], a2 = offs2[pair];
+    const uint64_t len1 = offs1[pair + 1] - a1, len2 = offs2[pair + 1] - a2;
+    const uint8_t *r1 = bases1 + a1, *r2 = bases2 + a2;
+    const int8_t *qa = q1 ? q1 + a1 : nullptr, *qb = q2 ? q2 + a2 : nullptr;
+    const uint64_t d1 = noffs1[pair], m = noffs1[pair + 1] - d1, d2 = noffs2[pair];
+    const int k = kind[pair];
+    const uint64_t off = k ? (uint64_t)offset[pair] : 0;
+    if (k == 0) {
+      for (uint64_t i = lane; i < len1; i += 64) { ob1[d1 + i] = r1[i]; if (oq1 && qa) oq1[d1 + i] = qa[i]; }
+      for (uint64_t i = lane; i < len2; i += 64) { ob2[d2 + i] = r2[i]; if (oq2 && qb) oq2[d2 + i] = qb[i]; }
+    } else if (k == 2) {                  // read through: r1[0 .. overlapSize), the mate's base where its quality is higher or r1 has 'N'
+      for (uint64_t i = lane; i < m; i += 64) {
+        uint8_t c = r1[i];
+        int8_t q = 0;
+        if (qa) {
+          q = qa[i];
+          const uint64_t p = len2 - 1 - (i + off);
+          const int8_t mq = qb[p];
+          if (mq > q || c == 'N') { c = merge_comp_char(r2[p]); q = mq; }
+        }
+        ob1[d1 + i] = c;
+        if (oq1 && qa) oq1[d1 + i] = q;
+      }
+    } else {                              // overlap: offset + len2 bases; r1's base in front of the overlap, and inside it unless the mate's quality wins by more than 14
+      for (uint64_t i = lane; i < m; i += 64) {
+        uint8_t c = 0;
+        int8_t q = 0;
+        bool take_r1 = i < off;
+        if (!take_r1) {
+          const uint64_t p = len2 - 1 - (i - off);
+          c = merge_comp_char(r2[p]);
+          if (qb) q = qb[p];
+          take_r1 = i < len1 && ((qa && (int)qa[i] >= (int)q - 14) || c == 'N');
+        }
+        if (take_r1) { c = r1[i]; if (qa) q = qa[i]; }
+        ob1[d1 + i] = c;
+        if (oq1 && qa) oq1[d1 + i] = q;
+      }
+    }
+  }
+}
+
 }  // namespace cfr

@@ -27,4 +27,11 @@ const char *tax_rank_string(uint8_t rank);
 void dust_mask(uint8_t *s, size_t n);
 void dust_mask_literal(uint8_t *s, size_t n);
 
+// --merge-readpair pre-step (cfr_merge.cpp): ReadPairMerger::Merge for one pair, and the table of its thresholds below 100 bases
+constexpr int kMergeThrTable = 100;
+void merge_threshold_table(int32_t t[kMergeThrTable]);
+struct MergeScratch { std::vector<char> rcr2; std::vector<int8_t> rcq2; };
+int merge_pair(const uint8_t *r1, const int8_t *q1, int len1, const uint8_t *r2, const int8_t *q2, int len2, uint8_t *rm, int8_t *qm,
+               int *mlen, int *overlap, int *offset, MergeScratch &ws);
+
 }  // namespace cfr

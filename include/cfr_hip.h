@@ -302,6 +302,46 @@ cfr_status cfr_dust_mask_batch_literal(uint8_t *bases, const uint64_t *offsets, 
 cfr_status cfr_device_index_set_dust(cfr_dev_index *d, int on);
 cfr_status cfr_dust_mask_device(cfr_dev_index *d, uint8_t *bases, const uint64_t *offsets, size_t n);
 
+/* ---- --merge-readpair: overlapping mates merged into one read before SDUST and Query (ReadPairMerger::Merge,
+ * ReadPairMerger.hpp:132-233, called at CentrifugerClass.cpp:271-273) ----
+ * A pair whose mates overlap (kind 1) or whose fragment is shorter than the reads (read-through, kind 2) becomes
+ * read 1 = the merged read, read 2 = empty; the result of classifying that pair is the reference's Query(rm, NULL).  Every other
+ * pair (kind 0) stays as it is.  qual1 / qual2: the quality characters of the mates, laid out by the same offsets as the bases;
+ * both NULL for FASTA input, and CFR_ERR_ARG when only one is given (the reference dereferences a null pointer there).
+ *
+ * cfr_merge_pairs: the merge on `threads` host threads (the literal restatement of the reference; what the kernels are tested
+ *   against).  out_bases1 / out_qual1: room for total1 + total2 bytes; out_bases2 / out_qual2: total2 bytes; out_offsets*: n + 1
+ *   entries.  kind / overlap / offset (n entries each, any may be NULL): the return value of Merge and what it leaves in
+ *   overlapSize / offset (for kind 0: -1 and the last offset that passed either test, or -1).  out_qual* may be NULL (always without
+ *   qualities): the merged qualities are then not handed out.
+ * cfr_merge_pairs_device: the same through the device kernels, host buffers in and out (parity probe). */
+cfr_status cfr_merge_pairs(const uint8_t *bases1, const uint64_t *offsets1, const char *qual1,
+                           const uint8_t *bases2, const uint64_t *offsets2, const char *qual2, size_t n, int threads,
+                           uint8_t *out_bases1, uint64_t *out_offsets1, char *out_qual1,
+                           uint8_t *out_bases2, uint64_t *out_offsets2, char *out_qual2,
+                           int32_t *kind, int32_t *overlap, int32_t *offset);
+cfr_status cfr_merge_pairs_device(cfr_dev_index *d, const uint8_t *bases1, const uint64_t *offsets1, const char *qual1,
+                                  const uint8_t *bases2, const uint64_t *offsets2, const char *qual2, size_t n,
+                                  uint8_t *out_bases1, uint64_t *out_offsets1, char *out_qual1,
+                                  uint8_t *out_bases2, uint64_t *out_offsets2, char *out_qual2,
+                                  int32_t *kind, int32_t *overlap, int32_t *offset);
+/* cfr_device_index_set_merge(d, 1): every following cfr_classify_batch_merged / cfr_classify_batch_resident_merged call on d merges
+ * its pairs in HBM first (then SDUST when cfr_device_index_set_dust is on, then the search); the caller's buffers are not modified.
+ * Switched off (the default) those two calls are cfr_classify_batch / cfr_classify_batch_resident.  A single-end batch is classified
+ * as it is either way.  The other entries never merge; cfr_classify_batch_packed returns CFR_ERR_ARG while the switch is on (the
+ * packed form cannot tell 'N' from other bytes, the merge compares them).  CFR_ERR_ARG on a protein index.
+ * merge_kind: n entries (may be NULL), the kind of every pair (all 0 when nothing was merged).
+ * cfr_last_merge_ms: device time of the merge pre-step of the last such call (0 when it did not run). */
+cfr_status cfr_device_index_set_merge(cfr_dev_index *d, int on);
+cfr_status cfr_classify_batch_merged(cfr_dev_index *d, const uint8_t *bases1, const uint64_t *offsets1, const char *qual1,
+                                     const uint8_t *bases2, const uint64_t *offsets2, const char *qual2, size_t n,
+                                     cfr_result *results, cfr_match *matches, size_t match_cap, size_t *n_matches, int32_t *merge_kind);
+cfr_status cfr_classify_batch_resident_merged(cfr_dev_index *d, const void *d_bases1, const void *d_offsets1, const void *d_qual1,
+                                              const void *d_bases2, const void *d_offsets2, const void *d_qual2, size_t n,
+                                              uint64_t total_bases1, uint64_t total_bases2,
+                                              cfr_result *results, cfr_match *matches, size_t match_cap, size_t *n_matches, int32_t *merge_kind);
+cfr_status cfr_last_merge_ms(const cfr_dev_index *d, float *ms);
+
 /* ResultWriter::Output rows for one read (ResultWriter.hpp:209-240).  Returns bytes needed (without the NUL); writes at most cap and always
  * NUL-terminates a non-empty buffer: a return value >= cap means the text was cut at cap - 1 and the caller retries with value + 1. */
 size_t cfr_format_tsv(const cfr_index *idx, const char *read_id, const cfr_result *r, const cfr_match *matches,
