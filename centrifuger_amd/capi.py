@@ -95,6 +95,8 @@ EXPORTS = [
     "cfr_classify_batch_expanded", "cfr_classify_from_hits_expanded", "cfr_format_tsv_expanded", "cfr_tsv_header_expanded",
     "cfr_merge_pairs", "cfr_merge_pairs_device", "cfr_device_index_set_merge", "cfr_classify_batch_merged",
     "cfr_classify_batch_resident_merged", "cfr_last_merge_ms",
+    "cfr_quant_options_default", "cfr_quant_open", "cfr_quant_add_tsv", "cfr_quant_add_results", "cfr_quant_assignments", "cfr_quant_run",
+    "cfr_quant_values", "cfr_quant_write", "cfr_quant_get_stats", "cfr_quant_destroy",
 ]
 
 _lib = None
@@ -117,8 +119,11 @@ def lib():
         L.cfr_host_free.argtypes = [C.c_void_p]
         for name in EXPORTS:
             if name not in ("cfr_last_error", "cfr_version", "cfr_tsv_header", "cfr_format_tsv", "cfr_index_destroy", "cfr_format_tsv_expanded", "cfr_tsv_header_expanded",
-                            "cfr_device_index_destroy", "cfr_params_default", "cfr_host_alloc", "cfr_host_free", "cfr_build_options_default"):
+                            "cfr_device_index_destroy", "cfr_params_default", "cfr_host_alloc", "cfr_host_free", "cfr_build_options_default",
+                            "cfr_quant_options_default", "cfr_quant_destroy"):
                 getattr(L, name).restype = C.c_int
+        L.cfr_quant_destroy.restype = None
+        L.cfr_quant_destroy.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -654,3 +659,78 @@ class PinnedArray:
             self.array = None
             lib().cfr_host_free(C.c_void_p(self._p))
             self._p = None
+
+
+class QuantOptions(C.Structure):
+    _fields_ = [("min_score", C.c_uint64), ("min_length", C.c_int32), ("device", C.c_int32), ("table_slots", C.c_uint64),
+                ("threads", C.c_int32), ("pad", C.c_int32)]
+
+
+class QuantStats(C.Structure):
+    _fields_ = [("reader_ms", C.c_double), ("coalesce_ms", C.c_double), ("em_ms", C.c_double), ("grow_count", C.c_uint64),
+                ("table_slots", C.c_uint64), ("em_rounds", C.c_int32), ("pad", C.c_int32)]
+
+
+class Quant:
+    """cfr_quant: abundance estimation (centrifuger-quant).  device=None: the host twin, no GPU is touched."""
+
+    def __init__(self, prefix: str, device=0, min_score=0, min_length=0, table_slots=0, threads=0):
+        opt = QuantOptions()
+        lib().cfr_quant_options_default(C.byref(opt))
+        opt.min_score, opt.min_length, opt.table_slots, opt.threads = min_score, min_length, table_slots, threads
+        opt.device = -1 if device is None else device
+        self._q = C.c_void_p()
+        _check(lib().cfr_quant_open(prefix.encode(), C.byref(opt), C.byref(self._q)))
+
+    def add_tsv(self, path: str):
+        _check(lib().cfr_quant_add_tsv(self._q, path.encode()))
+
+    def add_results(self, results, matches):
+        results = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
+        matches = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        _check(lib().cfr_quant_add_results(self._q, _p(results), _p(matches), C.c_size_t(len(results))))
+
+    def assignments(self):
+        """(lists, weight, count, uniq): lists = tuples of compact tax ids in the reference's order"""
+        n = C.c_size_t()
+        pb, pt, pw, pc, pu = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_double)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+        _check(lib().cfr_quant_assignments(self._q, C.byref(n), C.byref(pb), C.byref(pt), C.byref(pw), C.byref(pc), C.byref(pu)))
+        n = n.value
+        begin = np.ctypeslib.as_array(pb, shape=(n + 1,)).copy()
+        targets = np.ctypeslib.as_array(pt, shape=(max(int(begin[n]), 1),))[:int(begin[n])].copy() if n else np.zeros(0, dtype=np.uint32)
+        lists = [tuple(int(x) for x in targets[int(begin[i]):int(begin[i + 1])]) for i in range(n)]
+        arr = lambda p: np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0)   # noqa: E731
+        return lists, arr(pw), arr(pc), arr(pu)
+
+    def run(self) -> int:
+        rounds = C.c_int32()
+        _check(lib().cfr_quant_run(self._q, C.byref(rounds)))
+        return rounds.value
+
+    def values(self):
+        """dict of abund, read_count, uniq_count (float64) and taxid_length (uint64), node_cnt + 1 entries each"""
+        pa, pr, pu, pl, nc = C.POINTER(C.c_double)(), C.POINTER(C.c_double)(), C.POINTER(C.c_double)(), C.POINTER(C.c_uint64)(), C.c_uint64()
+        _check(lib().cfr_quant_values(self._q, C.byref(pa), C.byref(pr), C.byref(pu), C.byref(pl), C.byref(nc)))
+        n = nc.value + 1
+        return {"abund": np.ctypeslib.as_array(pa, shape=(n,)).copy(), "read_count": np.ctypeslib.as_array(pr, shape=(n,)).copy(),
+                "uniq_count": np.ctypeslib.as_array(pu, shape=(n,)).copy(), "taxid_length": np.ctypeslib.as_array(pl, shape=(n,)).copy(),
+                "node_cnt": nc.value}
+
+    def write(self, path: str, fmt: int = 0):
+        _check(lib().cfr_quant_write(self._q, C.c_int(fmt), path.encode()))
+
+    def stats(self) -> QuantStats:
+        st = QuantStats()
+        _check(lib().cfr_quant_get_stats(self._q, C.byref(st)))
+        return st
+
+    def close(self):
+        if self._q:
+            lib().cfr_quant_destroy(self._q)
+            self._q = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -13,9 +13,11 @@
 
 #include "cfr_build.hpp"
 #include "cfr_device.hpp"
+#include "cfr_quant.hpp"
 #include "cfr_tail.hpp"
 
 struct cfr_index { cfr::HostIndex *h; };
+struct cfr_quant { cfr::Quant *q; std::vector<double> weight; int32_t rounds = 0; bool ran = false; };
 // One call at a time per device image: `busy` is held for the length of every entry that touches the image (try_lock:
 // CFR_ERR_BUSY for the second caller) and by the worker thread while it runs a submitted batch.
 struct cfr_async_job { std::function<cfr_status(std::string &, size_t &)> run; uint64_t ticket; };
@@ -549,6 +551,101 @@ cfr_status cfr_dust_mask_device(cfr_dev_index *d, uint8_t *bases, const uint64_t
     d->d->dust_mask_host(bases, offsets, n);
     return CFR_OK;
   });
+}
+
+// ---- centrifuger-quant ----
+void cfr_quant_options_default(cfr_quant_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  o->device = 0;
+}
+
+cfr_status cfr_quant_open(const char *idx_prefix, const cfr_quant_options *o, cfr_quant **out) {
+  if (!idx_prefix || !out) return bad_arg("cfr_quant_open: null argument");
+  *out = nullptr;
+  return guarded([&]() -> cfr_status {
+    cfr::QuantOptions qo;
+    if (o) { qo.min_score = o->min_score; qo.min_length = o->min_length; qo.device = o->device; qo.table_slots = o->table_slots; qo.threads = o->threads; }
+    else qo.device = 0;
+    cfr_quant *q = new cfr_quant();
+    try { q->q = new cfr::Quant(idx_prefix, qo); } catch (...) { delete q; throw; }
+    *out = q;
+    return CFR_OK;
+  });
+}
+
+cfr_status cfr_quant_add_tsv(cfr_quant *q, const char *path) {
+  if (!q || !path) return bad_arg("cfr_quant_add_tsv: null argument");
+  return guarded([&]() -> cfr_status { q->q->add_tsv(path); return CFR_OK; });
+}
+
+cfr_status cfr_quant_add_results(cfr_quant *q, const cfr_result *r, const cfr_match *m, size_t n) {
+  if (!q || (n && (!r || !m))) return bad_arg("cfr_quant_add_results: null argument");
+  return guarded([&]() -> cfr_status { q->q->add_results(r, m, n); return CFR_OK; });
+}
+
+cfr_status cfr_quant_assignments(cfr_quant *q, size_t *n, const uint64_t **begin, const uint32_t **targets, const double **weight,
+                                 const uint64_t **count, const uint64_t **uniq) {
+  if (!q || !n) return bad_arg("cfr_quant_assignments: null argument");
+  return guarded([&]() -> cfr_status {
+    const cfr::QuantAssignments &a = q->q->assignments();
+    q->weight.resize(a.n());
+    for (size_t i = 0; i < a.n(); ++i) q->weight[i] = (double)a.weight_units[i] / (double)(1ull << cfr::kQuantWeightShift);
+    *n = a.n();
+    if (begin) *begin = a.begin.data();
+    if (targets) *targets = a.targets.data();
+    if (weight) *weight = q->weight.data();
+    if (count) *count = a.count.data();
+    if (uniq) *uniq = a.uniq.data();
+    return CFR_OK;
+  });
+}
+
+cfr_status cfr_quant_run(cfr_quant *q, int32_t *em_rounds) {
+  if (!q) return bad_arg("cfr_quant_run: null argument");
+  return guarded([&]() -> cfr_status {
+    q->rounds = q->q->run();
+    q->ran = true;
+    if (em_rounds) *em_rounds = q->rounds;
+    return CFR_OK;
+  });
+}
+
+cfr_status cfr_quant_values(const cfr_quant *q, const double **abund, const double **read_count, const double **uniq_count,
+                            const uint64_t **taxid_length, uint64_t *node_cnt) {
+  if (!q) return bad_arg("cfr_quant_values: null argument");
+  if (abund) *abund = q->q->abund().data();
+  if (read_count) *read_count = q->q->read_count().data();
+  if (uniq_count) *uniq_count = q->q->uniq_count().data();
+  if (taxid_length) *taxid_length = q->q->taxid_length().data();
+  if (node_cnt) *node_cnt = q->q->node_cnt();
+  return CFR_OK;
+}
+
+cfr_status cfr_quant_write(const cfr_quant *q, int format, const char *path) {
+  if (!q || !path) return bad_arg("cfr_quant_write: null argument");
+  if (!q->ran) return bad_arg("cfr_quant_write: cfr_quant_run has not been called");
+  const bool to_stdout = !strcmp(path, "-");
+  FILE *fp = to_stdout ? stdout : fopen(path, "w");
+  if (!fp) { g_err = std::string("cannot write ") + path; return CFR_ERR_IO; }
+  q->q->write(fp, format);
+  if (to_stdout) fflush(fp); else fclose(fp);
+  return CFR_OK;
+}
+
+cfr_status cfr_quant_get_stats(const cfr_quant *q, cfr_quant_stats *st) {
+  if (!q || !st) return bad_arg("cfr_quant_get_stats: null argument");
+  memset(st, 0, sizeof(*st));
+  st->reader_ms = q->q->reader_ms; st->coalesce_ms = q->q->coalesce_ms; st->em_ms = q->q->em_ms;
+  const cfr::QuantDeviceStats d = q->q->device_stats();
+  st->grow_count = d.grow_count; st->table_slots = d.table_slots; st->em_rounds = q->rounds;
+  return CFR_OK;
+}
+
+void cfr_quant_destroy(cfr_quant *q) {
+  if (!q) return;
+  delete q->q;
+  delete q;
 }
 
 // ---- --merge-readpair ----

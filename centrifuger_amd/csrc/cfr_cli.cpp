@@ -58,6 +58,9 @@ const char *kUsage =
     "\t--hitk-factor INT: resolve at most <int>*k entries for each hit [40; use 0 for no restriction]\n"
     "\t--consider-secondary STR: in the format INT,FLOAT consider the secondary hit if its hitlen>=INT,score>=FLOAT*best_score [2000,0.995]\n"
     "\t--expand-taxid: output the tax IDs that are promoted to the final report tax ID [no]\n"
+    "\t--quant FILE: also write the abundance report of centrifuger-quant for this run to FILE (equal to centrifuger-quant -x IDX -c\n"
+    "\t\tthis output, when no two adjacent reads share a read id: there every read is an assignment of its own) [no report]\n"
+    "\t--quant-format INT: format of that report (0:centrifuge, 1:metaphlan, 2:CAMI, 3:kraken-report) [0]\n"
     "\t--gpu LIST: comma separated MI355X ordinals, or 'all' [0]\n"
     "\t--gpu-batch INT: reads per device batch [262144]\n"
     "\t--gpu-balanced: also derive the text-mode tables and the locate memo on the device (+0.4 s load per Gbp, faster kernels)\n"
@@ -66,7 +69,7 @@ const char *kUsage =
     "\t-h: print this usage message\n"
     "\t-v: print the version information and quit\n";
 
-enum { OPT_UN = 1000, OPT_CL, OPT_NO_DUST, OPT_MIN_HITLEN, OPT_HITK, OPT_SECONDARY, OPT_GPU, OPT_GPU_BATCH, OPT_GPU_THROUGHPUT, OPT_GPU_FASTLOAD, OPT_GPU_BALANCED, OPT_PARSE_THREADS, OPT_EXPAND_TAXID, OPT_MERGE_READPAIR, OPT_UNSUPPORTED };
+enum { OPT_UN = 1000, OPT_CL, OPT_NO_DUST, OPT_MIN_HITLEN, OPT_HITK, OPT_SECONDARY, OPT_GPU, OPT_GPU_BATCH, OPT_GPU_THROUGHPUT, OPT_GPU_FASTLOAD, OPT_GPU_BALANCED, OPT_PARSE_THREADS, OPT_EXPAND_TAXID, OPT_MERGE_READPAIR, OPT_QUANT, OPT_QUANT_FORMAT, OPT_UNSUPPORTED };
 
 void print_log(const char *fmt, ...) {   // Utils::PrintLog (compactds/Utils.hpp:369-381)
   char buffer[1024];
@@ -673,6 +676,8 @@ struct Options {
   cfr_params params;
   bool dust = true;
   bool merge = false;                  // --merge-readpair
+  std::string quant_path;              // --quant: the abundance report of this run
+  int quant_format = 0;                // --quant-format
   std::string un_prefix, cl_prefix;
   std::vector<int> gpus{0};
   bool all_gpus = false;
@@ -734,6 +739,7 @@ int main(int argc, char *argv[]) {
       {"gpu-fast-load", no_argument, 0, OPT_GPU_FASTLOAD}, {"gpu-balanced", no_argument, 0, OPT_GPU_BALANCED},
       {"parse-threads", required_argument, 0, OPT_PARSE_THREADS},
       {"sample-sheet", required_argument, 0, OPT_UNSUPPORTED}, {"merge-readpair", no_argument, 0, OPT_MERGE_READPAIR},
+      {"quant", required_argument, 0, OPT_QUANT}, {"quant-format", required_argument, 0, OPT_QUANT_FORMAT},
       {"expand-taxid", no_argument, 0, OPT_EXPAND_TAXID}, {"read-format", required_argument, 0, OPT_UNSUPPORTED},
       {"barcode", required_argument, 0, OPT_UNSUPPORTED}, {"UMI", required_argument, 0, OPT_UNSUPPORTED},
       {"barcode-whitelist", required_argument, 0, OPT_UNSUPPORTED}, {"barcode-translate", required_argument, 0, OPT_UNSUPPORTED},
@@ -754,6 +760,8 @@ int main(int argc, char *argv[]) {
       case OPT_CL: opt.cl_prefix = optarg; break;
       case OPT_NO_DUST: opt.dust = false; break;
       case OPT_MERGE_READPAIR: opt.merge = true; break;                    // CentrifugerClass.cpp:445-447
+      case OPT_QUANT: opt.quant_path = optarg; break;
+      case OPT_QUANT_FORMAT: opt.quant_format = atoi(optarg); break;
       case OPT_EXPAND_TAXID: opt.params.output_expanded = 1; break;       // CentrifugerClass.cpp:453-455
       case OPT_MIN_HITLEN: opt.params.min_hit_len = atoi(optarg); break;
       case OPT_HITK: opt.params.max_result_per_hit_factor = atoi(optarg); break;
@@ -1273,6 +1281,19 @@ int main(int argc, char *argv[]) {
   fputs(expand ? cfr_tsv_header_expanded() : cfr_tsv_header(), stdout);          // only once the index and the devices are up: a failed load prints no TSV at all
 
 
+  // --quant: the quantifier of centrifuger-quant beside the classifier (Quantifier::AddReadAssignment, Quantifier.hpp:624-637): every
+  // batch's results go into it on the worker that holds them; it coalesces them in the HBM of the first GPU of the run
+  cfr_quant *quant = nullptr;
+  std::mutex quant_mu;
+  if (!opt.quant_path.empty()) {
+    if (opt.quant_format < 0 || opt.quant_format > 3) { print_log("ERROR: --quant-format takes 0, 1, 2 or 3."); return EXIT_FAILURE; }
+    cfr_quant_options qo;
+    cfr_quant_options_default(&qo);
+    qo.device = opt.gpus[0];
+    cfr_status s = cfr_quant_open(opt.idx.c_str(), &qo, &quant);
+    if (s != CFR_OK) die_status("cfr_quant_open", s);
+  }
+
   // device stage: one thread per GPU takes dust-masked batches
   auto worker = [&](cfr_dev_index *dev) {
     for (;;) {
@@ -1312,6 +1333,11 @@ int main(int argc, char *argv[]) {
         if (s == CFR_ERR_CAPACITY) { if (used > cap) cap = used + 16; if (ids_used > ids_cap) ids_cap = ids_used + 16; continue; }
         if (s != CFR_OK) die_status("cfr_classify_batch", s);
         break;
+      }
+      if (quant) {
+        std::lock_guard<std::mutex> ql(quant_mu);
+        cfr_status s = cfr_quant_add_results(quant, b->results.data(), b->matches.data(), b->n);
+        if (s != CFR_OK) die_status("cfr_quant_add_results", s);
       }
       clk.add(T_CLASSIFY, ts);
       std::lock_guard<std::mutex> lk(mu);
@@ -1414,6 +1440,13 @@ int main(int argc, char *argv[]) {
   // ResultWriter::Finalize (ResultWriter.hpp:279-283)
   print_log("Processed %lu read fragments, and %lu (%.2lf%%) can be classified.", (unsigned long)total, (unsigned long)classified,
             total ? (double)classified / (double)total * 100.0 : 0.0);
+  if (quant) {
+    cfr_status s = cfr_quant_run(quant, nullptr);
+    if (s != CFR_OK) die_status("cfr_quant_run", s);
+    s = cfr_quant_write(quant, opt.quant_format, opt.quant_path.c_str());
+    if (s != CFR_OK) die_status("cfr_quant_write", s);
+    cfr_quant_destroy(quant);
+  }
   for (auto *d : devs) cfr_device_index_destroy(d);
   cfr_index_destroy(idx);
   clk.add(T_WALL, t_wall);

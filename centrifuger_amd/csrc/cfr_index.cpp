@@ -478,10 +478,12 @@ void parse_taxonomy(const std::string &path, Taxonomy &t) {
   t.extra_seq_cnt = c.get<uint64_t>();
   t.parent.resize(t.node_cnt);
   t.rank.resize(t.node_cnt);
+  t.leaf.resize(t.node_cnt);
   for (uint64_t i = 0; i < t.node_cnt; ++i) {   // TaxonomyNode: u64 parent | u8 rank | u8 leaf | u8 pad[6]
     t.parent[i] = c.get<uint64_t>();
     t.rank[i] = c.get<uint8_t>();
-    c.skip(7);
+    t.leaf[i] = c.get<uint8_t>();
+    c.skip(6);
   }
   uint64_t map_n = c.get<uint64_t>();
   t.orig_taxid.resize(map_n);
@@ -510,6 +512,9 @@ bool is_protein(const std::string &prefix) {   // Classifier::IsProteinDatabase 
 }
 
 }  // namespace
+
+// the taxonomy alone, for the quantifier (cfr_quant.cpp): no .1.cfr is opened
+void load_taxonomy(const std::string &path, Taxonomy &t) { parse_taxonomy(path, t); }
 
 uint64_t index_digest(const HostIndex &h) {
   uint64_t x = 1469598103934665603ull;

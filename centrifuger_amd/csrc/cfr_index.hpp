@@ -71,6 +71,7 @@ struct Taxonomy {
   uint64_t node_cnt = 0, seq_cnt = 0, extra_seq_cnt = 0, root = 0;
   std::vector<uint64_t> parent;
   std::vector<uint8_t> rank;
+  std::vector<uint8_t> leaf;    // TaxonomyNode::leaf (read by the quantifier's genome lengths, Taxonomy.hpp:1179)
   std::vector<uint64_t> orig_taxid;
   std::vector<std::string> tax_name;
   std::vector<uint64_t> seq_to_tax;

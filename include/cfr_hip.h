@@ -353,6 +353,56 @@ size_t cfr_format_tsv_expanded(const cfr_index *idx, const char *read_id, const 
                                const cfr_span *spans, const uint64_t *ids, char *buf, size_t cap);
 const char *cfr_tsv_header_expanded(void);
 
+/* ---- centrifuger-quant: abundance estimation from read assignments (Quantifier, Quantifier.hpp; CentrifugerQuant.cpp) ----
+ * cfr_quant_open reads <prefix>.2.cfr (taxonomy) and <prefix>.3.cfr (sequence lengths) only - never the FM index - and computes the
+ * genome length of every tax id (Taxonomy::ConvertSeqLengthToTaxLength, Taxonomy.hpp:1111-1213).
+ *   reference                                                      this library
+ *   Quantifier::Init(idxPrefix)             Quantifier.hpp:432-458   cfr_quant_open
+ *   Quantifier::LoadReadAssignments         :515-622                 cfr_quant_add_tsv      (plain, gz, "-" = stdin; several calls add up)
+ *   Quantifier::AddReadAssignment           :624-637                 cfr_quant_add_results  (+ the filter of LoadReadAssignments)
+ *   CoalesceAssignments                     :490-513                 cfr_quant_assignments  (device: k_quant_coalesce)
+ *   Quantification / EstimateAbundanceWithEM :640-743, 186-281       cfr_quant_run          (device: the E-step of every round)
+ *   Quantifier::Output                      :746-818                 cfr_quant_write
+ * options.device >= 0: records are coalesced in that GPU's HBM and the E-step of every EM round runs there (CFR_ERR_NO_DEVICE
+ * without it: no fall-back); device = -1: the host twin alone, no GPU is touched.  Both give the same bits: the coalesce sums
+ * integers (a weight is 4^-d, d <= 11, summed in units of 2^-22), the E-step keeps the reference's order of additions.
+ * A handle is used by one thread at a time. */
+typedef struct cfr_quant cfr_quant;
+typedef struct {
+  uint64_t min_score;     /* --min-score: rows below it are dropped */
+  int32_t min_length;     /* --min-length: rows whose hitLength is below it are dropped */
+  int32_t device;         /* HIP device ordinal; -1: host twin only */
+  uint64_t table_slots;   /* slots of the device coalesce table at the start (rounded up to a power of two, at least 64); 0 = default.
+                             The table grows when it is half full: a small value only makes a test meet that path */
+  int32_t threads;        /* threads of the TSV reader; 0 = automatic (at most 16) */
+  int32_t pad;
+} cfr_quant_options;
+typedef struct {
+  double reader_ms, coalesce_ms, em_ms;   /* wall time spent reading rows, coalescing (device: upload, kernels, growth, download; sort), in cfr_quant_run */
+  uint64_t grow_count, table_slots;       /* device coalesce table: times it was grown, slots at the end (0 on the host twin) */
+  int32_t em_rounds, pad;
+} cfr_quant_stats;
+void cfr_quant_options_default(cfr_quant_options *o);
+cfr_status cfr_quant_open(const char *idx_prefix, const cfr_quant_options *o, cfr_quant **out);
+/* rows of a classification TSV: the first line is the header; consecutive kept rows with one read id are one assignment */
+cfr_status cfr_quant_add_tsv(cfr_quant *q, const char *path);
+/* results as cfr_classify_batch left them: every read is its own assignment; n_match == 0 is unclassified; the filter and the weight
+ * of the TSV path (score, hit_length, query_length, secondary_score) apply */
+cfr_status cfr_quant_add_results(cfr_quant *q, const cfr_result *r, const cfr_match *m, size_t n);
+/* The coalesced assignments in the reference's order (by size, then by the targets in order): list i is
+ * targets[begin[i] .. begin[i + 1]) - compact tax ids, node_cnt for a tax id the tree does not hold.  The arrays belong to q.
+ * Nothing can be added after this call or cfr_quant_run. */
+cfr_status cfr_quant_assignments(cfr_quant *q, size_t *n, const uint64_t **begin, const uint32_t **targets, const double **weight,
+                                 const uint64_t **count, const uint64_t **uniq);
+cfr_status cfr_quant_run(cfr_quant *q, int32_t *em_rounds);
+/* after cfr_quant_run: abund / read_count / uniq_count have node_cnt + 1 entries (compact tax ids), taxid_length node_cnt + 1; any may be NULL */
+cfr_status cfr_quant_values(const cfr_quant *q, const double **abund, const double **read_count, const double **uniq_count,
+                            const uint64_t **taxid_length, uint64_t *node_cnt);
+/* format 0..3 as --output-format (0 centrifuge, 1 metaphlan, 2 CAMI, 3 kraken-report); path "-" = stdout */
+cfr_status cfr_quant_write(const cfr_quant *q, int format, const char *path);
+cfr_status cfr_quant_get_stats(const cfr_quant *q, cfr_quant_stats *st);
+void cfr_quant_destroy(cfr_quant *q);
+
 /* ---- index writer (outside the classification path) ----
  * What `centrifuger-build` produces (Builder::Build + FMBuilder, Builder.hpp:86-313, compactds/FMBuilder.hpp:209-313):
  * <out_prefix>.{1,2,3,4}.cfr for nucleotide sequences, default layout options (--rbbwt-b / --offrate / --ftabchars
