@@ -97,6 +97,10 @@ EXPORTS = [
     "cfr_classify_batch_resident_merged", "cfr_last_merge_ms",
     "cfr_quant_options_default", "cfr_quant_open", "cfr_quant_add_tsv", "cfr_quant_add_results", "cfr_quant_assignments", "cfr_quant_run",
     "cfr_quant_values", "cfr_quant_write", "cfr_quant_get_stats", "cfr_quant_destroy",
+    "cfr_read_format_parse", "cfr_read_format_info", "cfr_read_format_extract", "cfr_read_format_destroy",
+    "cfr_barcode_open", "cfr_barcode_count", "cfr_barcode_correct", "cfr_barcode_correct_host", "cfr_barcode_counts", "cfr_barcode_get_stats",
+    "cfr_barcode_destroy", "cfr_barcode_translate_open", "cfr_barcode_translate_apply", "cfr_barcode_translate_destroy",
+    "cfr_tsv_header_ex", "cfr_format_tsv_ex",
 ]
 
 _lib = None
@@ -120,10 +124,14 @@ def lib():
         for name in EXPORTS:
             if name not in ("cfr_last_error", "cfr_version", "cfr_tsv_header", "cfr_format_tsv", "cfr_index_destroy", "cfr_format_tsv_expanded", "cfr_tsv_header_expanded",
                             "cfr_device_index_destroy", "cfr_params_default", "cfr_host_alloc", "cfr_host_free", "cfr_build_options_default",
-                            "cfr_quant_options_default", "cfr_quant_destroy"):
+                            "cfr_quant_options_default", "cfr_quant_destroy", "cfr_read_format_destroy", "cfr_barcode_destroy",
+                            "cfr_barcode_translate_destroy", "cfr_tsv_header_ex", "cfr_format_tsv_ex"):
                 getattr(L, name).restype = C.c_int
-        L.cfr_quant_destroy.restype = None
-        L.cfr_quant_destroy.argtypes = [C.c_void_p]
+        for name in ("cfr_quant_destroy", "cfr_read_format_destroy", "cfr_barcode_destroy", "cfr_barcode_translate_destroy"):
+            getattr(L, name).restype = None
+            getattr(L, name).argtypes = [C.c_void_p]
+        L.cfr_tsv_header_ex.restype = C.c_char_p
+        L.cfr_format_tsv_ex.restype = C.c_size_t
         _lib = L
     return _lib
 
@@ -255,6 +263,19 @@ class Index:
         if n >= len(buf):
             buf = C.create_string_buffer(n + 1)
             lib().cfr_format_tsv(self._h, read_id.encode(), _p(r), _p(matches), buf, C.c_size_t(len(buf)))
+        return buf.raw[:n]
+
+    def format_tsv_ex(self, read_id: str, result, matches, has_barcode=False, barcode=None, has_umi=False, umi=None, expanded=False,
+                      spans=None, ids=None) -> bytes:
+        """cfr_format_tsv_ex: the row(s) of one read with the barcode / UMI columns (barcode / umi: bytes, None = a bare tab)"""
+        r = np.ascontiguousarray(result).reshape(1)
+        buf = C.create_string_buffer(1 << 16)
+        args = (self._h, read_id.encode(), _p(r), _p(matches), C.c_int(int(has_barcode)), C.c_char_p(barcode), C.c_int(int(has_umi)), C.c_char_p(umi),
+                C.c_int(int(expanded)), _p(spans), _p(ids))
+        n = lib().cfr_format_tsv_ex(*args, buf, C.c_size_t(len(buf)))
+        if n >= len(buf):
+            buf = C.create_string_buffer(n + 1)
+            lib().cfr_format_tsv_ex(*args, buf, C.c_size_t(len(buf)))
         return buf.raw[:n]
 
     def format_tsv_expanded(self, read_id: str, result, matches, spans, ids) -> bytes:
@@ -642,6 +663,10 @@ def tsv_header() -> bytes:
     return lib().cfr_tsv_header()
 
 
+def tsv_header_ex(has_barcode=False, has_umi=False, expanded=False) -> bytes:
+    return lib().cfr_tsv_header_ex(C.c_int(int(has_barcode)), C.c_int(int(has_umi)), C.c_int(int(expanded)))
+
+
 class PinnedArray:
     """numpy view over cfr_host_alloc memory (pinned: D2H lands at PCIe rate)."""
 
@@ -728,6 +753,137 @@ class Quant:
         if self._q:
             lib().cfr_quant_destroy(self._q)
             self._q = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+FORMAT_READ1, FORMAT_READ2, FORMAT_BARCODE, FORMAT_UMI = 0, 1, 2, 3
+
+
+class ReadFormat:
+    """cfr_read_format: a --read-format string (ReadFormatter).  CfrError(CFR_ERR_FORMAT, "Format description error in ...") for a bad one."""
+
+    def __init__(self, spec: str):
+        self._f = C.c_void_p()
+        _check(lib().cfr_read_format_parse(spec.encode(), C.byref(self._f)))
+
+    def info(self, category: int):
+        """(segment count, NeedExtract, IsInComment)"""
+        a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
+        _check(lib().cfr_read_format_info(self._f, C.c_int(category), C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, bool(b.value), bool(c.value)
+
+    def extract(self, category: int, bases, offsets, qual=None, comments=None, comment_offsets=None, inplace=True):
+        """cfr_read_format_extract -> (bases, offsets, qual or None)"""
+        bases, offsets, qual, comments, comment_offsets = _u8(bases), _u64(offsets), _u8(qual), _u8(comments), _u64(comment_offsets)
+        n = len(offsets if offsets is not None else comment_offsets) - 1
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        head = (self._f, C.c_int(category), C.c_int(int(inplace)), _p(bases), _p(offsets), _p(qual), _p(comments), _p(comment_offsets), C.c_size_t(n))
+        _check(lib().cfr_read_format_extract(*head, None, _p(out_off), None))
+        out = np.zeros(max(int(out_off[n]), 1), dtype=np.uint8)
+        oq = np.zeros(len(out), dtype=np.uint8) if qual is not None and not self.info(category)[2] else None
+        _check(lib().cfr_read_format_extract(*head, _p(out), _p(out_off), _p(oq)))
+        total = int(out_off[n])
+        return out[:total], out_off, (None if oq is None else oq[:total])
+
+    def close(self):
+        if self._f:
+            lib().cfr_read_format_destroy(self._f)
+            self._f = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BarcodeStats(C.Structure):
+    _fields_ = [("whitelist_size", C.c_uint64), ("table_slots", C.c_uint64), ("host_barcodes", C.c_uint64), ("host_barcodes_total", C.c_uint64),
+                ("device_ms", C.c_double), ("barcode_length", C.c_int32), ("on_device", C.c_int32)]
+
+
+class Barcode:
+    """cfr_barcode: a barcode whitelist (BarcodeCorrector).  device=None: the host twin only, no GPU is touched."""
+
+    def __init__(self, whitelist_path: str, device=0):
+        self._b = C.c_void_p()
+        _check(lib().cfr_barcode_open(whitelist_path.encode(), C.c_int(-1 if device is None else device), C.byref(self._b)))
+
+    def count(self, bases, offsets, max_records=2000000):
+        bases, offsets = _u8(bases), _u64(offsets)
+        _check(lib().cfr_barcode_count(self._b, _p(bases), _p(offsets), C.c_size_t(len(offsets) - 1), C.c_size_t(max_records)))
+
+    def _correct(self, fn, bases, offsets, qual, threads):
+        bases, offsets, qual = _u8(bases), _u64(offsets), _u8(qual)
+        n = len(offsets) - 1
+        status = np.zeros(n, dtype=np.int8)
+        out = np.zeros(max(len(bases), 1), dtype=np.uint8)
+        _check(fn(self._b, _p(bases), _p(offsets), _p(qual), C.c_size_t(n), C.c_int(threads), _p(status), _p(out)))
+        return status, out[:len(bases)]
+
+    def correct(self, bases, offsets, qual=None, threads=1):
+        """cfr_barcode_correct (the handle's path) -> (status int8[n], bases after the call)"""
+        return self._correct(lib().cfr_barcode_correct, bases, offsets, qual, threads)
+
+    def correct_host(self, bases, offsets, qual=None, threads=1):
+        """cfr_barcode_correct_host: always the host twin"""
+        return self._correct(lib().cfr_barcode_correct_host, bases, offsets, qual, threads)
+
+    def counts(self):
+        """(entries as a list of bytes, counts uint32) in sorted order"""
+        n, pb, po, pc = C.c_size_t(), C.POINTER(C.c_uint8)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint32)()
+        _check(lib().cfr_barcode_counts(self._b, C.byref(n), C.byref(pb), C.byref(po), C.byref(pc)))
+        n = n.value
+        off = np.ctypeslib.as_array(po, shape=(n + 1,)).copy()
+        total = int(off[n])
+        flat = bytes(np.ctypeslib.as_array(pb, shape=(max(total, 1),))[:total]) if n else b""
+        cnt = np.ctypeslib.as_array(pc, shape=(n,)).copy() if n else np.zeros(0, dtype=np.uint32)
+        return [flat[int(off[i]):int(off[i + 1])] for i in range(n)], cnt
+
+    def stats(self) -> BarcodeStats:
+        st = BarcodeStats()
+        _check(lib().cfr_barcode_get_stats(self._b, C.byref(st)))
+        return st
+
+    def close(self):
+        if self._b:
+            lib().cfr_barcode_destroy(self._b)
+            self._b = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BarcodeTranslate:
+    """cfr_barcode_translate: a --barcode-translate table (BarcodeTranslator)."""
+
+    def __init__(self, path: str):
+        self._t = C.c_void_p()
+        _check(lib().cfr_barcode_translate_open(path.encode(), C.byref(self._t)))
+
+    def apply(self, bases, offsets, status=None):
+        """-> (bases, offsets); CfrError with the reference's message for a piece that is not in the table"""
+        bases, offsets = _u8(bases), _u64(offsets)
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int8)
+        n = len(offsets) - 1
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        _check(lib().cfr_barcode_translate_apply(self._t, _p(bases), _p(offsets), _p(status), C.c_size_t(n), None, _p(out_off)))
+        out = np.zeros(max(int(out_off[n]), 1), dtype=np.uint8)
+        _check(lib().cfr_barcode_translate_apply(self._t, _p(bases), _p(offsets), _p(status), C.c_size_t(n), _p(out), _p(out_off)))
+        return out[:int(out_off[n])], out_off
+
+    def close(self):
+        if self._t:
+            lib().cfr_barcode_translate_destroy(self._t)
+            self._t = C.c_void_p()
 
     def __del__(self):
         try:

@@ -1,22 +1,28 @@
 // cfr_capi.cpp — the extern "C" surface declared in include/cfr_hip.h.
+#include <algorithm>
 #include <condition_variable>
 #include <cstdio>
 #include <cstring>
 #include <deque>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <string>
 #include <thread>
 #include <vector>
 
+#include "cfr_barcode.hpp"
 #include "cfr_build.hpp"
 #include "cfr_device.hpp"
 #include "cfr_quant.hpp"
 #include "cfr_tail.hpp"
 
 struct cfr_index { cfr::HostIndex *h; };
+struct cfr_read_format { cfr::ReadFormat f; };
+struct cfr_barcode { cfr::Barcode *b; };
+struct cfr_barcode_translate { cfr::BarcodeTranslate *t; };
 struct cfr_quant { cfr::Quant *q; std::vector<double> weight; int32_t rounds = 0; bool ran = false; };
 // One call at a time per device image: `busy` is held for the length of every entry that touches the image (try_lock:
 // CFR_ERR_BUSY for the second caller) and by the worker thread while it runs a submitted batch.
@@ -648,6 +654,166 @@ void cfr_quant_destroy(cfr_quant *q) {
   delete q;
 }
 
+// ---- single-cell input: read formats, barcode whitelist, barcode translation ----
+cfr_status cfr_read_format_parse(const char *spec, cfr_read_format **out) {
+  if (!spec || !out) return bad_arg("cfr_read_format_parse: null argument");
+  *out = nullptr;
+  return guarded([&]() -> cfr_status {
+    std::unique_ptr<cfr_read_format> f(new cfr_read_format());
+    if (!f->f.init(spec)) throw cfr::FormatError{std::string("Format description error in ") + spec};   // ReadFormatter.hpp:212
+    *out = f.release();
+    return CFR_OK;
+  });
+}
+
+cfr_status cfr_read_format_info(const cfr_read_format *f, int category, int32_t *n_segments, int32_t *need_extract, int32_t *in_comment) {
+  if (!f || category < 0 || category >= cfr::kFormatCategories) return bad_arg("cfr_read_format_info: bad argument");
+  if (n_segments) *n_segments = f->f.segment_count(category);
+  if (need_extract) *need_extract = f->f.need_extract(category) ? 1 : 0;
+  if (in_comment) *in_comment = f->f.in_comment(category) ? 1 : 0;
+  return CFR_OK;
+}
+
+cfr_status cfr_read_format_extract(const cfr_read_format *f, int category, int inplace, const uint8_t *bases, const uint64_t *offsets, const char *qual,
+                                   const uint8_t *comments, const uint64_t *comment_offsets, size_t n, uint8_t *out_bases, uint64_t *out_offsets,
+                                   char *out_qual) {
+  if (!f || !out_offsets || category < 0 || category >= cfr::kFormatCategories) return bad_arg("cfr_read_format_extract: bad argument");
+  const bool hd = f->f.in_comment(category);
+  if (n && (hd ? (!comments || !comment_offsets) : (!bases || !offsets))) return bad_arg("cfr_read_format_extract: null argument");
+  const uint8_t *src = hd ? comments : bases;
+  const uint64_t *off = hd ? comment_offsets : offsets;
+  for (size_t i = 0; i < n; ++i)
+    if (off[i + 1] < off[i] || off[i + 1] - off[i] > 0x7fffffffull) return bad_arg("cfr_read_format_extract: offsets must not decrease, records stay below 2^31 bytes");
+  return guarded([&]() -> cfr_status {
+    std::string s, q;
+    out_offsets[0] = 0;
+    for (size_t i = 0; i < n; ++i) {
+      const char *p = (const char *)src + off[i];
+      const size_t len = (size_t)(off[i + 1] - off[i]);
+      const bool with_qual = !hd && qual && out_qual && out_bases;
+      if (hd || !inplace) {                                  // Extract(.., needComplement = true, .., bufferId 0) (CentrifugerClass.cpp:182, BarcodeCorrector.hpp:156)
+        f->f.extract(p, len, category, true, s);
+        if (with_qual) f->f.extract(qual + offsets[i], len, category, false, q);
+      } else {                                               // InplaceExtractSeqAndQual (ReadFormatter.hpp:408-422)
+        s.assign(p, len);
+        f->f.extract_inplace(s, category, true);
+        if (with_qual) { q.assign(qual + offsets[i], len); f->f.extract_inplace(q, category, false); }
+      }
+      if (out_bases) {
+        memcpy(out_bases + out_offsets[i], s.data(), s.size());
+        if (with_qual) memcpy(out_qual + out_offsets[i], q.data(), std::min(q.size(), s.size()));
+      }
+      out_offsets[i + 1] = out_offsets[i] + s.size();
+    }
+    return CFR_OK;
+  });
+}
+
+void cfr_read_format_destroy(cfr_read_format *f) { delete f; }
+
+cfr_status cfr_barcode_open(const char *whitelist_path, int device, cfr_barcode **out) {
+  if (!whitelist_path || !out) return bad_arg("cfr_barcode_open: null argument");
+  *out = nullptr;
+  return guarded([&]() -> cfr_status {
+    std::unique_ptr<cfr_barcode> b(new cfr_barcode{nullptr});
+    b->b = new cfr::Barcode(whitelist_path, device);
+    *out = b.release();
+    return CFR_OK;
+  });
+}
+
+static cfr_status barcode_args(const char *who, const cfr_barcode *bc, const uint8_t *bases, const uint64_t *offsets, size_t n) {
+  if (!bc || (n && (!bases || !offsets))) { g_err = std::string(who) + ": null argument"; return CFR_ERR_ARG; }
+  for (size_t i = 0; i < n; ++i) {
+    if (offsets[i + 1] < offsets[i]) { g_err = std::string(who) + ": offsets must not decrease"; return CFR_ERR_ARG; }
+    if (offsets[i + 1] - offsets[i] > cfr::kBarcodeMaxLen) { g_err = std::string(who) + ": a barcode of 256 bytes or more (BarcodeCorrector's buffer holds 255)"; return CFR_ERR_ARG; }
+  }
+  return CFR_OK;
+}
+
+cfr_status cfr_barcode_count(cfr_barcode *bc, const uint8_t *bases, const uint64_t *offsets, size_t n, size_t max_records) {
+  if (n > max_records) n = max_records;
+  if (cfr_status st = barcode_args("cfr_barcode_count", bc, bases, offsets, n)) return st;
+  return guarded([&]() -> cfr_status { bc->b->count(bases, offsets, n, max_records); return CFR_OK; });
+}
+
+static cfr_status barcode_correct(const char *who, cfr_barcode *bc, const uint8_t *bases, const uint64_t *offsets, const char *qual, size_t n, int threads,
+                                  int8_t *status, uint8_t *out_bases, bool host_only) {
+  if (cfr_status st = barcode_args(who, bc, bases, offsets, n)) return st;
+  if (n && (!status || !out_bases)) { g_err = std::string(who) + ": null argument"; return CFR_ERR_ARG; }
+  return guarded([&]() -> cfr_status { bc->b->correct(bases, offsets, (const int8_t *)qual, n, threads, status, out_bases, host_only); return CFR_OK; });
+}
+
+cfr_status cfr_barcode_correct(cfr_barcode *bc, const uint8_t *bases, const uint64_t *offsets, const char *qual, size_t n, int threads, int8_t *status,
+                               uint8_t *out_bases) {
+  return barcode_correct("cfr_barcode_correct", bc, bases, offsets, qual, n, threads, status, out_bases, false);
+}
+
+cfr_status cfr_barcode_correct_host(cfr_barcode *bc, const uint8_t *bases, const uint64_t *offsets, const char *qual, size_t n, int threads, int8_t *status,
+                                    uint8_t *out_bases) {
+  return barcode_correct("cfr_barcode_correct_host", bc, bases, offsets, qual, n, threads, status, out_bases, true);
+}
+
+cfr_status cfr_barcode_counts(cfr_barcode *bc, size_t *n_entries, const uint8_t **bases, const uint64_t **offsets, const uint32_t **counts) {
+  if (!bc || !n_entries || !bases || !offsets || !counts) return bad_arg("cfr_barcode_counts: null argument");
+  return guarded([&]() -> cfr_status { bc->b->counts(bases, offsets, counts, n_entries); return CFR_OK; });
+}
+
+cfr_status cfr_barcode_get_stats(const cfr_barcode *bc, cfr_barcode_stats *st) {
+  if (!bc || !st) return bad_arg("cfr_barcode_get_stats: null argument");
+  memset(st, 0, sizeof(*st));
+  st->whitelist_size = bc->b->whitelist().size();
+  st->table_slots = bc->b->table_slots();
+  st->host_barcodes = bc->b->host_barcodes;
+  st->host_barcodes_total = bc->b->host_barcodes_total;
+  st->device_ms = bc->b->device_ms;
+  st->barcode_length = bc->b->whitelist().common_length();
+  st->on_device = bc->b->on_device() ? 1 : 0;
+  return CFR_OK;
+}
+
+void cfr_barcode_destroy(cfr_barcode *bc) {
+  if (!bc) return;
+  delete bc->b;
+  delete bc;
+}
+
+cfr_status cfr_barcode_translate_open(const char *path, cfr_barcode_translate **out) {
+  if (!path || !out) return bad_arg("cfr_barcode_translate_open: null argument");
+  *out = nullptr;
+  return guarded([&]() -> cfr_status {
+    std::unique_ptr<cfr_barcode_translate> t(new cfr_barcode_translate{nullptr});
+    t->t = new cfr::BarcodeTranslate(path);
+    *out = t.release();
+    return CFR_OK;
+  });
+}
+
+cfr_status cfr_barcode_translate_apply(const cfr_barcode_translate *t, const uint8_t *bases, const uint64_t *offsets, const int8_t *status, size_t n,
+                                       uint8_t *out_bases, uint64_t *out_offsets) {
+  if (!t || !out_offsets || (n && (!bases || !offsets))) return bad_arg("cfr_barcode_translate_apply: null argument");
+  for (size_t i = 0; i < n; ++i)
+    if (offsets[i + 1] < offsets[i]) return bad_arg("cfr_barcode_translate_apply: offsets must not decrease");
+  return guarded([&]() -> cfr_status {
+    std::string s, missing;
+    out_offsets[0] = 0;
+    for (size_t i = 0; i < n; ++i) {
+      if (status && status[i] == -1) s = "N";                 // CentrifugerClass.cpp:201-205
+      else if (!t->t->translate(bases + offsets[i], (size_t)(offsets[i + 1] - offsets[i]), s, missing))
+        throw cfr::FormatError{"Barcode " + missing + " does not exist in the translation table."};   // BarcodeTranslator.hpp:70
+      if (out_bases) memcpy(out_bases + out_offsets[i], s.data(), s.size());
+      out_offsets[i + 1] = out_offsets[i] + s.size();
+    }
+    return CFR_OK;
+  });
+}
+
+void cfr_barcode_translate_destroy(cfr_barcode_translate *t) {
+  if (!t) return;
+  delete t->t;
+  delete t;
+}
+
 // ---- --merge-readpair ----
 static cfr_status merge_args(const char *who, const void *bases1, const void *offsets1, const void *qual1, const void *bases2, const void *offsets2,
                              const void *qual2, size_t n) {
@@ -792,18 +958,35 @@ const char *cfr_tsv_header_expanded(void) {   // ... with _outputExpandedTaxIds 
   return "readID\tseqID\ttaxID\tscore\t2ndBestScore\thitLength\tqueryLength\tnumMatches\texpandedTaxIDs\n";
 }
 
-static size_t format_tsv(const cfr_index *idx, const char *read_id, const cfr_result *r, const cfr_match *matches, bool expanded, const cfr_span *spans,
-                         const uint64_t *ids, char *buf, size_t cap);
+const char *cfr_tsv_header_ex(int has_barcode, int has_umi, int expanded) {   // ... with _hasBarcode / _hasUmi (ResultWriter.hpp:190-193)
+#define CFR_TSV_HEAD "readID\tseqID\ttaxID\tscore\t2ndBestScore\thitLength\tqueryLength\tnumMatches"
+  static const char *const kHeader[8] = {CFR_TSV_HEAD "\n", CFR_TSV_HEAD "\tbarcode\n", CFR_TSV_HEAD "\tUMI\n", CFR_TSV_HEAD "\tbarcode\tUMI\n",
+                                         CFR_TSV_HEAD "\texpandedTaxIDs\n", CFR_TSV_HEAD "\tbarcode\texpandedTaxIDs\n", CFR_TSV_HEAD "\tUMI\texpandedTaxIDs\n",
+                                         CFR_TSV_HEAD "\tbarcode\tUMI\texpandedTaxIDs\n"};
+#undef CFR_TSV_HEAD
+  return kHeader[(has_barcode ? 1 : 0) | (has_umi ? 2 : 0) | (expanded ? 4 : 0)];
+}
+
+// the barcode / UMI columns of one row: absent, or PrintExtraCol(s) (ResultWriter.hpp:32-38: a bare tab for a null string)
+struct ExtraCols { bool has_barcode = false, has_umi = false; const char *barcode = nullptr, *umi = nullptr; };
+static size_t format_tsv(const cfr_index *idx, const char *read_id, const cfr_result *r, const cfr_match *matches, const ExtraCols &x, bool expanded,
+                         const cfr_span *spans, const uint64_t *ids, char *buf, size_t cap);
 size_t cfr_format_tsv(const cfr_index *idx, const char *read_id, const cfr_result *r, const cfr_match *matches, char *buf, size_t cap) {
-  return format_tsv(idx, read_id, r, matches, false, nullptr, nullptr, buf, cap);
+  return format_tsv(idx, read_id, r, matches, ExtraCols(), false, nullptr, nullptr, buf, cap);
 }
 size_t cfr_format_tsv_expanded(const cfr_index *idx, const char *read_id, const cfr_result *r, const cfr_match *matches, const cfr_span *spans,
                                const uint64_t *ids, char *buf, size_t cap) {
-  return format_tsv(idx, read_id, r, matches, true, spans, ids, buf, cap);
+  return format_tsv(idx, read_id, r, matches, ExtraCols(), true, spans, ids, buf, cap);
+}
+size_t cfr_format_tsv_ex(const cfr_index *idx, const char *read_id, const cfr_result *r, const cfr_match *matches, int has_barcode, const char *barcode,
+                         int has_umi, const char *umi, int expanded, const cfr_span *spans, const uint64_t *ids, char *buf, size_t cap) {
+  ExtraCols x;
+  x.has_barcode = has_barcode != 0; x.has_umi = has_umi != 0; x.barcode = barcode; x.umi = umi;
+  return format_tsv(idx, read_id, r, matches, x, expanded != 0, spans, ids, buf, cap);
 }
 
-static size_t format_tsv(const cfr_index *idx, const char *read_id, const cfr_result *r, const cfr_match *matches, bool expanded, const cfr_span *spans,
-                         const uint64_t *ids, char *buf, size_t cap) {
+static size_t format_tsv(const cfr_index *idx, const char *read_id, const cfr_result *r, const cfr_match *matches, const ExtraCols &x, bool expanded,
+                         const cfr_span *spans, const uint64_t *ids, char *buf, size_t cap) {
   // ResultWriter::Output (ResultWriter.hpp:209-240): "%s\t%s\t%lu\t%lu\t%lu\t%d\t%d\t%d" + PrintExtraCol(expandedTaxIdStrings[i]) / PrintExtraCol("")
   // (:226-227, :239-240) - the same bytes, put together by hand: at a hundred million rows per run snprintf's format parsing was the
   // command line's slowest stage (profiles/r5_cli_timing_100m.txt)
@@ -813,6 +996,10 @@ static size_t format_tsv(const cfr_index *idx, const char *read_id, const cfr_re
     void ch(char c) { if (buf && off < cap) buf[off] = c; ++off; }
     void u64(uint64_t v) { char t[24]; int k = 24; do { t[--k] = (char)('0' + v % 10); v /= 10; } while (v); put(t + k, (size_t)(24 - k)); }
     void i32(int32_t v) { if (v < 0) { ch('-'); u64((uint64_t)(-(int64_t)v)); } else u64((uint64_t)v); }
+    void extra(const ExtraCols &x) {
+      if (x.has_barcode) { ch('\t'); if (x.barcode) put(x.barcode, strlen(x.barcode)); }
+      if (x.has_umi) { ch('\t'); if (x.umi) put(x.umi, strlen(x.umi)); }
+    }
   } o{buf, cap, 0};
   const cfr::Taxonomy &t = idx->h->tax;
   const size_t idn = strlen(read_id);
@@ -824,6 +1011,7 @@ static size_t format_tsv(const cfr_index *idx, const char *read_id, const cfr_re
       else name = cfr::tax_rank_string(m.id < t.node_cnt ? t.rank[m.id] : 0);
       o.put(read_id, idn); o.ch('\t'); o.put(name, strlen(name)); o.ch('\t'); o.u64(m.taxid); o.ch('\t'); o.u64(r->score); o.ch('\t');
       o.u64(r->secondary_score); o.ch('\t'); o.i32(r->hit_length); o.ch('\t'); o.i32(r->query_length); o.ch('\t'); o.i32(r->n_match);
+      o.extra(x);
       if (expanded) {
         o.ch('\t');
         const cfr_span sp = spans ? spans[r->match_begin + (uint64_t)i] : cfr_span{0, 0};
@@ -833,6 +1021,7 @@ static size_t format_tsv(const cfr_index *idx, const char *read_id, const cfr_re
     }
   } else {
     o.put(read_id, idn); { static const char kUn[] = "\tunclassified\t0\t0\t0\t0\t"; o.put(kUn, sizeof(kUn) - 1); } o.i32(r->query_length); o.put("\t1", 2);
+    o.extra(x);
     if (expanded) o.ch('\t');
     o.ch('\n');
   }

@@ -24,6 +24,7 @@
 #include <cstring>
 #include <ctime>
 #include <deque>
+#include <iostream>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -58,6 +59,11 @@ const char *kUsage =
     "\t--hitk-factor INT: resolve at most <int>*k entries for each hit [40; use 0 for no restriction]\n"
     "\t--consider-secondary STR: in the format INT,FLOAT consider the secondary hit if its hitlen>=INT,score>=FLOAT*best_score [2000,0.995]\n"
     "\t--expand-taxid: output the tax IDs that are promoted to the final report tax ID [no]\n"
+    "\t--barcode STR: path to the barcode file\n"
+    "\t--UMI STR: path to the UMI file\n"
+    "\t--read-format STR: format for read, barcode and UMI files, e.g. r1:0:-1,r2:0:-1,bc:0:15,um:16:-1 for paired-end files with barcode and UMI\n"
+    "\t--barcode-whitelist STR: path to the barcode whitelist file\n"
+    "\t--barcode-translate STR: path to the barcode translation file\n"
     "\t--quant FILE: also write the abundance report of centrifuger-quant for this run to FILE (equal to centrifuger-quant -x IDX -c\n"
     "\t\tthis output, when no two adjacent reads share a read id: there every read is an assignment of its own) [no report]\n"
     "\t--quant-format INT: format of that report (0:centrifuge, 1:metaphlan, 2:CAMI, 3:kraken-report) [0]\n"
@@ -69,7 +75,7 @@ const char *kUsage =
     "\t-h: print this usage message\n"
     "\t-v: print the version information and quit\n";
 
-enum { OPT_UN = 1000, OPT_CL, OPT_NO_DUST, OPT_MIN_HITLEN, OPT_HITK, OPT_SECONDARY, OPT_GPU, OPT_GPU_BATCH, OPT_GPU_THROUGHPUT, OPT_GPU_FASTLOAD, OPT_GPU_BALANCED, OPT_PARSE_THREADS, OPT_EXPAND_TAXID, OPT_MERGE_READPAIR, OPT_QUANT, OPT_QUANT_FORMAT, OPT_UNSUPPORTED };
+enum { OPT_UN = 1000, OPT_CL, OPT_NO_DUST, OPT_MIN_HITLEN, OPT_HITK, OPT_SECONDARY, OPT_GPU, OPT_GPU_BATCH, OPT_GPU_THROUGHPUT, OPT_GPU_FASTLOAD, OPT_GPU_BALANCED, OPT_PARSE_THREADS, OPT_EXPAND_TAXID, OPT_MERGE_READPAIR, OPT_QUANT, OPT_QUANT_FORMAT, OPT_BARCODE, OPT_UMI, OPT_READ_FORMAT, OPT_BARCODE_WHITELIST, OPT_BARCODE_TRANSLATE, OPT_UNSUPPORTED };
 
 void print_log(const char *fmt, ...) {   // Utils::PrintLog (compactds/Utils.hpp:369-381)
   char buffer[1024];
@@ -132,6 +138,8 @@ bool ByteBuf::use_pinned = false;     // measured: hipHostMalloc of 40 MB per ba
 class SeqReader {
  public:
   explicit SeqReader(const std::vector<std::string> &files) : files_(files), buf_(1u << 24) {}
+  bool want_comment = false;           // keep the header's comment (what follows the id's delimiter; kseq's comment) of the last record read
+  std::string last_comment;
   static int inflate_threads;          // threads that inflate the blocks of a BGZF file side by side (1: every .gz through gzread)
   // a byte range of a memory-mapped plain file that starts at a record header (the parallel path: ParallelFiles below)
   SeqReader(const char *mem, size_t len) : mem_(mem), pos_(0), end_(len), eof_(true) {}
@@ -205,6 +213,7 @@ class SeqReader {
     size_t idn = e - 1;
     if (idn >= 2 && p[e - 2] == '/' && (p[e - 1] == '1' || p[e - 1] == '2')) idn -= 2;
     if (ids) { ids->insert(ids->end(), p + 1, p + 1 + idn); ids->push_back('\0'); }
+    if (want_comment) { if (e < n) last_comment.assign(p + e + 1, n - e - 1); else last_comment.clear(); }
     has_qual = false;
     size_t seq_n = 0;
     // kseq's grammar (kseq.h kseq_read): the sequence runs until a line that starts with '>', '@' or '+', whatever the
@@ -602,6 +611,16 @@ struct Batch {
   std::vector<uint8_t> m_bases1, m_bases2;
   std::vector<uint64_t> m_offs1, m_offs2;
   std::vector<int32_t> merge_kind;
+  // single-cell input: the barcode / UMI records as read (from their files, or a copy of read 1: CopyBatch), then after extraction;
+  // bc_str / um_str: what is printed (after correction and translation), NUL-terminated
+  ByteBuf bc_raw, um_raw;
+  std::vector<uint64_t> bc_raw_off, um_raw_off, bc_rawq_off, um_rawq_off, bc_cm_off, um_cm_off, r1_cm_off;
+  std::vector<char> bc_rawq, um_rawq, bc_cm, um_cm, r1_cm;
+  std::vector<uint8_t> bc, bc_q, um;
+  std::vector<uint64_t> bc_off, um_off;
+  bool bc_has_q = false;
+  std::vector<char> bc_str, um_str;
+  std::vector<size_t> bc_str_off, um_str_off;
   std::vector<cfr_result> results;
   std::vector<cfr_match> matches;
   std::vector<cfr_span> spans;         // --expand-taxid: per match slot, its list in exp_ids
@@ -615,6 +634,9 @@ struct Batch {
     n = 0; done = false;
     ids.clear(); id_off.clear(); qual1.clear(); qual2.clear(); q1_off.clear(); q2_off.clear(); has_qual.clear(); has_qual2.clear();
     bases1.clear(); bases2.clear(); offs1.clear(); offs2.clear(); n_parts = 0;
+    bc_raw.clear(); um_raw.clear(); bc_rawq.clear(); um_rawq.clear(); bc_cm.clear(); um_cm.clear(); r1_cm.clear();
+    for (auto *v : {&bc_raw_off, &um_raw_off, &bc_rawq_off, &um_rawq_off, &bc_cm_off, &um_cm_off, &r1_cm_off}) v->assign(1, 0);
+    bc_str.clear(); um_str.clear(); bc_str_off.clear(); um_str_off.clear();
   }
 };
 
@@ -685,12 +707,18 @@ struct Options {
   bool throughput_profile = false;
   int parse_threads = 0;               // 0 = automatic
   bool balanced_profile = false;
+  // single-cell input (CentrifugerClass.cpp:374-381)
+  std::vector<std::string> bc_files, um_files;
+  std::string read_format, whitelist, translate;
+  bool has_read_format = false;
 };
 
 // gz read dumps (ResultWriter::SetOutputReads, ResultWriter.hpp:126-176)
 struct ReadDump {
-  gzFile fp[2] = {nullptr, nullptr};
-  void open(const std::string &prefix, bool mate) {
+  gzFile fp[4] = {nullptr, nullptr, nullptr, nullptr};   // read 1, read 2, barcode, UMI
+  void open(const std::string &prefix, bool mate, bool has_barcode, bool has_umi) {
+    if (has_barcode) fp[2] = gzopen((prefix + "_bc.fa.gz").c_str(), "w1");   // always 'fa' for barcode and umi (ResultWriter.hpp:161-171)
+    if (has_umi) fp[3] = gzopen((prefix + "_um.fa.gz").c_str(), "w1");
     if (mate) {
       fp[0] = gzopen((prefix + "_1.fq.gz").c_str(), "w1");
       fp[1] = gzopen((prefix + "_2.fq.gz").c_str(), "w1");
@@ -705,6 +733,7 @@ struct ReadDump {
     if (!q) gzprintf(fp[k], ">%s\n%.*s\n", id, (int)n, (const char *)s);
     else gzprintf(fp[k], "@%s\n%.*s\n+\n%.*s\n", id, (int)n, (const char *)s, (int)qn, q);
   }
+  void put_extra(int k, const char *id, const char *s) { if (fp[k]) gzprintf(fp[k], ">%s\n%s\n", id, s); }   // ResultWriter.hpp:267-275
   void close() { for (auto &f : fp) if (f) { gzclose(f); f = nullptr; } }
 };
 
@@ -740,9 +769,9 @@ int main(int argc, char *argv[]) {
       {"parse-threads", required_argument, 0, OPT_PARSE_THREADS},
       {"sample-sheet", required_argument, 0, OPT_UNSUPPORTED}, {"merge-readpair", no_argument, 0, OPT_MERGE_READPAIR},
       {"quant", required_argument, 0, OPT_QUANT}, {"quant-format", required_argument, 0, OPT_QUANT_FORMAT},
-      {"expand-taxid", no_argument, 0, OPT_EXPAND_TAXID}, {"read-format", required_argument, 0, OPT_UNSUPPORTED},
-      {"barcode", required_argument, 0, OPT_UNSUPPORTED}, {"UMI", required_argument, 0, OPT_UNSUPPORTED},
-      {"barcode-whitelist", required_argument, 0, OPT_UNSUPPORTED}, {"barcode-translate", required_argument, 0, OPT_UNSUPPORTED},
+      {"expand-taxid", no_argument, 0, OPT_EXPAND_TAXID}, {"read-format", required_argument, 0, OPT_READ_FORMAT},
+      {"barcode", required_argument, 0, OPT_BARCODE}, {"UMI", required_argument, 0, OPT_UMI},
+      {"barcode-whitelist", required_argument, 0, OPT_BARCODE_WHITELIST}, {"barcode-translate", required_argument, 0, OPT_BARCODE_TRANSLATE},
       {0, 0, 0, 0}};
   int c, option_index = 0;
   while ((c = getopt_long(argc, argv, short_options, long_options, &option_index)) != -1) {
@@ -763,6 +792,11 @@ int main(int argc, char *argv[]) {
       case OPT_QUANT: opt.quant_path = optarg; break;
       case OPT_QUANT_FORMAT: opt.quant_format = atoi(optarg); break;
       case OPT_EXPAND_TAXID: opt.params.output_expanded = 1; break;       // CentrifugerClass.cpp:453-455
+      case OPT_BARCODE: opt.bc_files.push_back(optarg); break;             // CentrifugerClass.cpp:457-466
+      case OPT_UMI: opt.um_files.push_back(optarg); break;
+      case OPT_READ_FORMAT: opt.read_format = optarg; opt.has_read_format = true; break;
+      case OPT_BARCODE_WHITELIST: opt.whitelist = optarg; break;
+      case OPT_BARCODE_TRANSLATE: opt.translate = optarg; break;
       case OPT_MIN_HITLEN: opt.params.min_hit_len = atoi(optarg); break;
       case OPT_HITK: opt.params.max_result_per_hit_factor = atoi(optarg); break;
       case OPT_SECONDARY: {
@@ -819,6 +853,38 @@ int main(int argc, char *argv[]) {
     print_log("ERROR: -u, -1/-2 and -i cannot be combined in one run of this build.");
     return EXIT_FAILURE;
   }
+
+  // ---- single-cell input: --barcode, --UMI, --read-format, --barcode-whitelist, --barcode-translate (CentrifugerClass.cpp:457-466, 516-590)
+  cfr_read_format *fmt = nullptr;
+  if (cfr_read_format_parse(opt.read_format.c_str(), &fmt) != CFR_OK) {     // ReadFormatter::Init (ReadFormatter.hpp:212-213)
+    fprintf(stderr, "%s\n", cfr_last_error());
+    return 1;
+  }
+  auto fmt_info = [&](int cat, int which) { int32_t v[3] = {0, 0, 0}; cfr_read_format_info(fmt, cat, &v[0], &v[1], &v[2]); return v[which]; };
+  const bool has_barcode = !opt.bc_files.empty() || fmt_info(CFR_FORMAT_BARCODE, 0) > 0;   // :560-563
+  const bool has_umi = !opt.um_files.empty() || fmt_info(CFR_FORMAT_UMI, 0) > 0;
+  const bool bc_hd = fmt_info(CFR_FORMAT_BARCODE, 2) != 0, um_hd = fmt_info(CFR_FORMAT_UMI, 2) != 0;
+  const bool single_cell = has_barcode || has_umi || opt.has_read_format;
+  if (!opt.whitelist.empty() && opt.bc_files.empty()) {                      // :565-574
+    print_log("Barcode whitelist has to be used with --barcode option, so cases like piping input is not supported.");
+    return EXIT_FAILURE;
+  }
+  if (!opt.whitelist.empty() && bc_hd) {
+    // (the reference's background pass hands the barcode record's sequence to a format that describes its comment, BarcodeCorrector.hpp:156)
+    print_log("ERROR: --barcode-whitelist cannot be combined with a barcode taken from the header comment (bc:hd:) in this build.");
+    return EXIT_FAILURE;
+  }
+  if ((!opt.bc_files.empty() && opt.bc_files.size() != std::max(opt.u.size(), std::max(opt.m1.size(), opt.inter.size()))) ||
+      (!opt.um_files.empty() && opt.um_files.size() != std::max(opt.u.size(), std::max(opt.m1.size(), opt.inter.size())))) {
+    print_log("ERROR: --barcode / --UMI must be given once per read file.");
+    return EXIT_FAILURE;
+  }
+  cfr_barcode_translate *translate = nullptr;
+  if (!opt.translate.empty() && cfr_barcode_translate_open(opt.translate.c_str(), &translate) != CFR_OK) {
+    print_log("ERROR: %s", cfr_last_error());
+    return EXIT_FAILURE;
+  }
+  if (single_cell) opt.parse_threads = 1;      // the barcode and UMI files are read in step with the reads: the sequential reader
 
   if (const char *e = getenv("CFR_CLI_PARSE_ONLY")) if (atoi(e)) {
     // parser self-test hook (tests/test_host_cpu.py): records as "id<TAB>bases[<TAB>mate bases]<TAB>q|-" lines; no index, no device
@@ -913,8 +979,8 @@ int main(int argc, char *argv[]) {
   StageClock clk;
   const auto t_wall = tick();
   ReadDump un, cl;
-  if (!opt.un_prefix.empty()) un.open(opt.un_prefix, paired);
-  if (!opt.cl_prefix.empty()) cl.open(opt.cl_prefix, paired);
+  if (!opt.un_prefix.empty()) un.open(opt.un_prefix, paired, has_barcode, has_umi);
+  if (!opt.cl_prefix.empty()) cl.open(opt.cl_prefix, paired, has_barcode, has_umi);
   if (!opt.all_gpus && opt.gpus.empty()) { print_log("ERROR: no MI355X device selected."); return EXIT_FAILURE; }
   if (opt.all_gpus) {
     int cnt = 0;
@@ -939,7 +1005,76 @@ int main(int argc, char *argv[]) {
 
   std::thread reader([&]() {
     const bool interleaved = !opt.inter.empty();
-    const bool keep_qual = !opt.un_prefix.empty() || !opt.cl_prefix.empty() || opt.merge;      // (ReadPairMerger reads the qualities)
+    const bool keep_qual = !opt.un_prefix.empty() || !opt.cl_prefix.empty() || opt.merge || single_cell;   // (ReadPairMerger and BarcodeCorrector read the qualities)
+    std::unique_ptr<SeqReader> bc_reader, um_reader;
+    if (!opt.bc_files.empty()) { bc_reader.reset(new SeqReader(opt.bc_files)); bc_reader->want_comment = bc_hd; }
+    if (!opt.um_files.empty()) { um_reader.reset(new SeqReader(opt.um_files)); um_reader->want_comment = um_hd; }
+    const bool r1_comment = (has_barcode && !bc_reader && bc_hd) || (has_umi && !um_reader && um_hd);
+    // one record of the barcode / UMI file beside the read just taken (GetNextBatch, CentrifugerClass.cpp:129-161)
+    auto take_extra = [&](SeqReader *r, ByteBuf &raw, std::vector<uint64_t> &off, std::vector<char> &q, std::vector<uint64_t> &q_off, std::vector<char> &cm,
+                          std::vector<uint64_t> &cm_off, const char *what) {
+      bool hq = false;
+      if (!r->next(nullptr, raw, &q, hq)) { print_log("ERROR: The %s file and read file have different number of reads.", what); exit(EXIT_FAILURE); }
+      off.push_back(raw.size()); q_off.push_back(q.size());
+      if (r->want_comment) { cm.insert(cm.end(), r->last_comment.begin(), r->last_comment.end()); cm_off.push_back(cm.size()); }
+    };
+    // Reformat everything (CentrifugerClass.cpp:163-224) up to the correction, which waits for the GPU that classifies the batch
+    auto extract = [&](int cat, const uint8_t *bases, const std::vector<uint64_t> &off, const char *q, const char *cm, const std::vector<uint64_t> &cm_off,
+                       size_t n, std::vector<uint8_t> &out, std::vector<uint64_t> &out_off, std::vector<uint8_t> *out_q) {
+      static const uint8_t kNone[1] = {0};
+      out_off.resize(n + 1);
+      auto call = [&](uint8_t *ob, char *oq) {
+        const cfr_status s = cfr_read_format_extract(fmt, cat, 1, bases ? bases : kNone, off.data(), q, (const uint8_t *)(cm ? cm : (const char *)kNone), cm_off.data(), n,
+                                                     ob, out_off.data(), oq);
+        if (s != CFR_OK) die_status("cfr_read_format_extract", s);
+      };
+      call(nullptr, nullptr);
+      out.resize(out_off[n] + 1);
+      if (out_q) out_q->resize(out_off[n] + 1);
+      call(out.data(), out_q && q ? (char *)out_q->data() : nullptr);
+    };
+    auto strings = [](const std::vector<uint8_t> &bases, const std::vector<uint64_t> &off, size_t n, std::vector<char> &str, std::vector<size_t> &str_off) {
+      str.clear(); str_off.clear();
+      for (size_t i = 0; i < n; ++i) { str_off.push_back(str.size()); str.insert(str.end(), bases.begin() + off[i], bases.begin() + off[i + 1]); str.push_back('\0'); }
+    };
+    auto uniform_qual = [](const std::vector<uint64_t> &off, const std::vector<uint64_t> &q_off, size_t n) {   // qualities for every record, as long as the bases
+      bool same = q_off.size() == n + 1 && q_off[n] > 0;
+      for (size_t i = 0; same && i <= n; ++i) same = q_off[i] == off[i];
+      return same;
+    };
+    auto reformat = [&](Batch &b) {
+      if (!single_cell || b.n == 0) return;
+      std::vector<uint8_t> tmp, tmp_q;
+      std::vector<uint64_t> tmp_off;
+      std::vector<uint64_t> q1o(b.q1_off.begin(), b.q1_off.end()), q2o(b.q2_off.begin(), b.q2_off.end());
+      const bool q1_ok = uniform_qual(b.offs1, q1o, b.n), q2_ok = b.paired && uniform_qual(b.offs2, q2o, b.n);
+      // barcode and UMI first: without a file of their own they are cut from read 1 as it was read (CopyBatch, :140-160)
+      auto side = [&](int cat, bool hd, SeqReader *r, ByteBuf &raw, std::vector<uint64_t> &raw_off, std::vector<char> &rawq, std::vector<uint64_t> &rawq_off,
+                      std::vector<char> &cm, std::vector<uint64_t> &cm_off, std::vector<uint8_t> &out, std::vector<uint64_t> &out_off, std::vector<uint8_t> *out_q,
+                      bool *has_q) {
+        const uint8_t *src = r ? raw.data() : b.bases1.data();
+        const std::vector<uint64_t> &src_off = r ? raw_off : b.offs1;
+        const bool q_ok = r ? uniform_qual(raw_off, rawq_off, b.n) : q1_ok;
+        const char *q = !q_ok || hd ? nullptr : r ? rawq.data() : b.qual1.data();
+        extract(cat, src, src_off, q, r ? cm.data() : b.r1_cm.data(), r ? cm_off : b.r1_cm_off, b.n, out, out_off, out_q);
+        if (has_q) *has_q = q != nullptr;
+      };
+      if (has_barcode) side(CFR_FORMAT_BARCODE, bc_hd, bc_reader.get(), b.bc_raw, b.bc_raw_off, b.bc_rawq, b.bc_rawq_off, b.bc_cm, b.bc_cm_off, b.bc, b.bc_off, &b.bc_q, &b.bc_has_q);
+      if (has_umi) {
+        side(CFR_FORMAT_UMI, um_hd, um_reader.get(), b.um_raw, b.um_raw_off, b.um_rawq, b.um_rawq_off, b.um_cm, b.um_cm_off, b.um, b.um_off, nullptr, nullptr);
+        strings(b.um, b.um_off, b.n, b.um_str, b.um_str_off);
+      }
+      auto mate = [&](int cat, ByteBuf &bases, std::vector<uint64_t> &off, std::vector<char> &qual, std::vector<size_t> &q_off, bool q_ok) {
+        if (!fmt_info(cat, 1)) return;                       // NeedExtract
+        static const std::vector<uint64_t> none{0};
+        extract(cat, bases.data(), off, q_ok ? qual.data() : nullptr, nullptr, none, b.n, tmp, tmp_off, &tmp_q);
+        bases.clear(); bases.append(tmp.data(), tmp_off[b.n]);
+        off = tmp_off;
+        if (q_ok) { qual.assign((const char *)tmp_q.data(), (const char *)tmp_q.data() + tmp_off[b.n]); q_off.assign(tmp_off.begin(), tmp_off.end()); }
+      };
+      mate(CFR_FORMAT_READ1, b.bases1, b.offs1, b.qual1, b.q1_off, q1_ok);
+      if (b.paired) mate(CFR_FORMAT_READ2, b.bases2, b.offs2, b.qual2, b.q2_off, q2_ok);
+    };
     size_t seq_no = 0;
     std::atomic<size_t> bases_hint{0};
     auto fresh_batch = [&]() {
@@ -977,6 +1112,9 @@ int main(int argc, char *argv[]) {
       b.id_off.push_back(id_at);
       b.offs1.push_back(b.bases1.size());
       if (keep_qual) { b.q1_off.push_back(b.qual1.size()); b.has_qual.push_back(hq ? 1 : 0); }
+      if (r1_comment) { b.r1_cm.insert(b.r1_cm.end(), r1->last_comment.begin(), r1->last_comment.end()); b.r1_cm_off.push_back(b.r1_cm.size()); }
+      if (bc_reader) take_extra(bc_reader.get(), b.bc_raw, b.bc_raw_off, b.bc_rawq, b.bc_rawq_off, b.bc_cm, b.bc_cm_off, "barcode");
+      if (um_reader) take_extra(um_reader.get(), b.um_raw, b.um_raw_off, b.um_rawq, b.um_rawq_off, b.um_cm, b.um_cm_off, "UMI");
       ++b.n;
       return true;
     };
@@ -1005,6 +1143,12 @@ int main(int argc, char *argv[]) {
           bool hq2 = false;
           if (r2->next(nullptr, extra, nullptr, hq2)) { print_log("ERROR: The two mate-pair read files have different number of reads."); exit(EXIT_FAILURE); }
         }
+        if (!more) for (SeqReader *r : {bc_reader.get(), um_reader.get()}) {
+          ByteBuf extra;
+          bool hq2 = false;
+          if (r && r->next(nullptr, extra, nullptr, hq2)) { print_log("ERROR: The %s file and read file have different number of reads.", r == bc_reader.get() ? "barcode" : "UMI"); exit(EXIT_FAILURE); }
+        }
+        reformat(*b);
         clk.add(T_PARSE, tp);
         if (b->n == 0) break;
         publish(b);
@@ -1149,6 +1293,7 @@ int main(int argc, char *argv[]) {
       if (interleaved) r1.reset(new SeqReader(opt.inter));
       else if (paired) { r1.reset(new SeqReader(opt.m1)); r2.reset(new SeqReader(opt.m2)); }
       else r1.reset(new SeqReader(opt.u));
+      r1->want_comment = r1_comment;
       read_sequential(r1.get(), r2.get());
     }
     std::lock_guard<std::mutex> lk(mu);
@@ -1278,7 +1423,40 @@ int main(int argc, char *argv[]) {
   }
   clk.add(T_DEVICE, t0);
   const bool expand = opt.params.output_expanded != 0;
-  fputs(expand ? cfr_tsv_header_expanded() : cfr_tsv_header(), stdout);          // only once the index and the devices are up: a failed load prints no TSV at all
+  // the whitelist: one table per GPU in use, then the background counts of the first 2 000 000 barcode records on each of them
+  // (SetWhitelist + CollectBackgroundDistribution, CentrifugerClass.cpp:521-523, 565-569), before any batch is corrected
+  std::vector<cfr_barcode *> whitelists;
+  if (!opt.whitelist.empty()) {
+    for (int g : opt.gpus) {
+      cfr_barcode *w = nullptr;
+      if ((st = cfr_barcode_open(opt.whitelist.c_str(), g, &w)) != CFR_OK) die_status("cfr_barcode_open", st);
+      whitelists.push_back(w);
+    }
+    SeqReader rd(opt.bc_files);
+    ByteBuf raw;
+    std::vector<uint64_t> off, out_off;
+    std::vector<uint8_t> out;
+    size_t left = 2000000;
+    bool more = true;
+    while (more && left) {
+      raw.clear(); off.assign(1, 0);
+      bool hq = false;
+      while (off.size() - 1 < std::min<size_t>(left, 1u << 18)) { if (!rd.next(nullptr, raw, nullptr, hq)) { more = false; break; } off.push_back(raw.size()); }
+      const size_t n = off.size() - 1;
+      if (!n) break;
+      static const uint8_t kNone[1] = {0};
+      out_off.resize(n + 1);
+      for (int pass = 0; pass < 2; ++pass) {      // Extract into a buffer, as the background pass does (BarcodeCorrector.hpp:156)
+        if (pass) out.resize(out_off[n] + 1);
+        if ((st = cfr_read_format_extract(fmt, CFR_FORMAT_BARCODE, 0, raw.data() ? raw.data() : kNone, off.data(), nullptr, nullptr, nullptr, n, pass ? out.data() : nullptr,
+                                          out_off.data(), nullptr)) != CFR_OK) die_status("cfr_read_format_extract", st);
+      }
+      for (size_t i = 0; i < n; ++i) if (out_off[i + 1] - out_off[i] > 255) { print_log("ERROR: a barcode of 256 bases or more cannot be looked up in the whitelist."); exit(EXIT_FAILURE); }
+      for (cfr_barcode *w : whitelists) if ((st = cfr_barcode_count(w, out.data(), out_off.data(), n, n)) != CFR_OK) die_status("cfr_barcode_count", st);
+      left -= n;
+    }
+  }
+  fputs(single_cell ? cfr_tsv_header_ex(has_barcode, has_umi, expand) : expand ? cfr_tsv_header_expanded() : cfr_tsv_header(), stdout);   // only once the index and the devices are up: a failed load prints no TSV at all
 
 
   // --quant: the quantifier of centrifuger-quant beside the classifier (Quantifier::AddReadAssignment, Quantifier.hpp:624-637): every
@@ -1295,7 +1473,7 @@ int main(int argc, char *argv[]) {
   }
 
   // device stage: one thread per GPU takes dust-masked batches
-  auto worker = [&](cfr_dev_index *dev) {
+  auto worker = [&](cfr_dev_index *dev, size_t dev_no) {
     for (;;) {
       std::shared_ptr<Batch> b;
       {
@@ -1306,6 +1484,40 @@ int main(int argc, char *argv[]) {
         dusted.pop_front();
       }
       const auto ts = tick();
+      if (has_barcode && b->n) {        // Correct, Translate or "N" (CentrifugerClass.cpp:186-206), on the GPU that classifies the batch
+        std::vector<int8_t> status(b->n, 0);
+        std::vector<uint8_t> fixed;
+        const uint8_t *bc = b->bc.data();
+        if (!whitelists.empty()) {
+          for (size_t i = 0; i < b->n; ++i) if (b->bc_off[i + 1] - b->bc_off[i] > 255) { print_log("ERROR: a barcode of 256 bases or more cannot be looked up in the whitelist."); exit(EXIT_FAILURE); }
+          fixed.resize(b->bc_off[b->n] + 1);
+          const cfr_status s = cfr_barcode_correct(whitelists[dev_no], b->bc.data(), b->bc_off.data(), b->bc_has_q ? (const char *)b->bc_q.data() : nullptr, b->n,
+                                                   std::max(1, opt.threads / (int)devs.size()), status.data(), fixed.data());
+          if (s != CFR_OK) die_status("cfr_barcode_correct", s);
+          bc = fixed.data();
+        }
+        b->bc_str.clear(); b->bc_str_off.clear();
+        if (translate) {
+          std::vector<uint64_t> t_off(b->n + 1);
+          std::vector<uint8_t> t;
+          for (int pass = 0; pass < 2; ++pass) {
+            if (pass) t.resize(t_off[b->n] + 1);
+            if (cfr_barcode_translate_apply(translate, bc, b->bc_off.data(), status.data(), b->n, pass ? t.data() : nullptr, t_off.data()) != CFR_OK) {
+              std::cerr << cfr_last_error() << std::endl;          // BarcodeTranslator.hpp:70-72
+              fflush(stdout);
+              _exit(255);
+            }
+          }
+          for (size_t i = 0; i < b->n; ++i) { b->bc_str_off.push_back(b->bc_str.size()); b->bc_str.insert(b->bc_str.end(), t.begin() + t_off[i], t.begin() + t_off[i + 1]); b->bc_str.push_back('\0'); }
+        } else {
+          for (size_t i = 0; i < b->n; ++i) {
+            b->bc_str_off.push_back(b->bc_str.size());
+            if (status[i] == -1) b->bc_str.push_back('N');
+            else b->bc_str.insert(b->bc_str.end(), bc + b->bc_off[i], bc + b->bc_off[i + 1]);
+            b->bc_str.push_back('\0');
+          }
+        }
+      }
       b->results.resize(b->n);
       size_t cap = b->n * (size_t)(opt.params.max_result > 0 ? opt.params.max_result : 4) + 16, used = 0;
       size_t ids_cap = expand ? std::max<size_t>(b->exp_ids.size(), 4 * b->n + 16) : 0, ids_used = 0;
@@ -1349,7 +1561,7 @@ int main(int argc, char *argv[]) {
     cv.notify_all();
   };
   std::vector<std::thread> workers;
-  for (cfr_dev_index *d : devs) workers.emplace_back(worker, d);
+  for (size_t k = 0; k < devs.size(); ++k) workers.emplace_back(worker, devs[k], k);
 
   // format stage: TSV rows (ResultWriter::Output), formatted in parallel slices then concatenated in order
   std::thread formatter([&]() {
@@ -1376,6 +1588,9 @@ int main(int argc, char *argv[]) {
         b->part_hits[(size_t)t] = hits;
         char buf[8192];
         auto row = [&](size_t i, char *dst, size_t cap) {
+          if (single_cell)
+            return cfr_format_tsv_ex(idx, b->id(i), &b->results[i], b->matches.data(), has_barcode, has_barcode ? b->bc_str.data() + b->bc_str_off[i] : nullptr, has_umi,
+                                     has_umi ? b->um_str.data() + b->um_str_off[i] : nullptr, expand, b->spans.data(), b->exp_ids.data(), dst, cap);
           return expand ? cfr_format_tsv_expanded(idx, b->id(i), &b->results[i], b->matches.data(), b->spans.data(), b->exp_ids.data(), dst, cap)
                         : cfr_format_tsv(idx, b->id(i), &b->results[i], b->matches.data(), dst, cap);
         };
@@ -1425,6 +1640,8 @@ int main(int argc, char *argv[]) {
         dump->put(1, b->id(i), s2, b->offs2[i + 1] - b->offs2[i],
                   b->has_qual2[i] ? b->qual2.data() + b->q2_off[i] : nullptr, b->q2_off[i + 1] - b->q2_off[i]);
       }
+      if (has_barcode) dump->put_extra(2, b->id(i), b->bc_str.data() + b->bc_str_off[i]);
+      if (has_umi) dump->put_extra(3, b->id(i), b->um_str.data() + b->um_str_off[i]);
     }
     clk.add(T_WRITE, tw);
     std::lock_guard<std::mutex> lk(mu);
@@ -1447,6 +1664,7 @@ int main(int argc, char *argv[]) {
     if (s != CFR_OK) die_status("cfr_quant_write", s);
     cfr_quant_destroy(quant);
   }
+  for (auto *w : whitelists) cfr_barcode_destroy(w);
   for (auto *d : devs) cfr_device_index_destroy(d);
   cfr_index_destroy(idx);
   clk.add(T_WALL, t_wall);

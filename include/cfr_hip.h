@@ -403,6 +403,81 @@ cfr_status cfr_quant_write(const cfr_quant *q, int format, const char *path);
 cfr_status cfr_quant_get_stats(const cfr_quant *q, cfr_quant_stats *st);
 void cfr_quant_destroy(cfr_quant *q);
 
+/* ---- single-cell input: read formats, barcode whitelist, barcode translation (ReadFormatter.hpp, BarcodeCorrector.hpp,
+ * BarcodeTranslator.hpp; the flow of CentrifugerClass.cpp:163-224, :565-574) ----
+ * Handles of their own, independent of any cfr_dev_index; one call at a time per handle.  Barcodes, reads and comments are flat
+ * byte arrays with n + 1 offsets, as everywhere in this header.
+ *
+ * cfr_read_format_parse: ReadFormatter::Init on `r1|r2|bc|um:START:END[:STRAND]` and `bc:hd:FIELD|PREFIX:START:END`, separated by
+ *   ',' or ';'.  CFR_ERR_FORMAT with the reference's "Format description error in <spec>" for what it refuses.
+ * cfr_read_format_info: segment count, NeedExtract, IsInComment of one category (any pointer may be NULL).
+ * cfr_read_format_extract: one category over n records.  inplace = 1: InplaceExtractSeqAndQual (what the classifier does to reads,
+ *   barcodes and UMIs); inplace = 0: Extract into a buffer of its own (what the background pass of the whitelist does).  A category
+ *   whose first segment is an `hd:` one is cut from `comments` (Extract on the comment; no qualities come out).  Bases are
+ *   complemented after a strand '-', qualities only reversed.  out_offsets (n + 1, from 0) is always written; with out_bases NULL
+ *   nothing else is: call once for the sizes, once for the bytes.  qual / out_qual / comments may be NULL. */
+typedef struct cfr_read_format cfr_read_format;
+enum { CFR_FORMAT_READ1 = 0, CFR_FORMAT_READ2 = 1, CFR_FORMAT_BARCODE = 2, CFR_FORMAT_UMI = 3 };
+cfr_status cfr_read_format_parse(const char *spec, cfr_read_format **out);
+cfr_status cfr_read_format_info(const cfr_read_format *f, int category, int32_t *n_segments, int32_t *need_extract, int32_t *in_comment);
+cfr_status cfr_read_format_extract(const cfr_read_format *f, int category, int inplace, const uint8_t *bases, const uint64_t *offsets,
+                                   const char *qual, const uint8_t *comments, const uint64_t *comment_offsets, size_t n,
+                                   uint8_t *out_bases, uint64_t *out_offsets, char *out_qual);
+void cfr_read_format_destroy(cfr_read_format *f);
+
+/* cfr_barcode_open: BarcodeCorrector::SetWhitelist (plain or gz).  device >= 0: when every valid entry has one length L <= 32 the
+ *   whitelist is also built as a hash table in the HBM of that device (cfr_barcode.hip) and cfr_barcode_count / cfr_barcode_correct
+ *   run there; a barcode whose length is not L, and every barcode of a whitelist of mixed lengths or L > 32, goes through the host
+ *   twin (a trie as in the reference) - the stats count them.  device = -1: host only, no GPU is touched.
+ * cfr_barcode_count: CollectBackgroundDistribution over the first min(n, max_records) barcodes (already extracted): + 1 for every
+ *   barcode that is on the list; calls add up.  max_records caps THIS call: a caller that feeds the pass in several calls keeps
+ *   the remainder of the reference's 2 000 000 itself.
+ * cfr_barcode_correct: BarcodeCorrector::Correct per barcode.  status[i]: 0 on the list (this includes a proper prefix of an entry
+ *   and, with it, the empty barcode), 1 corrected by one substitution, -1 not correctable (the classifier then prints "N").
+ *   out_bases: the barcodes after the call, same offsets.  qual may be NULL.  threads: host threads of the twin and of the copy.
+ * cfr_barcode_correct_host: the same through the twin whatever the handle holds.
+ * A barcode of 256 bytes or more is CFR_ERR_ARG (the reference's buffer ends there).
+ * cfr_barcode_counts: every entry and its count (whitelist lines + background hits), sorted (A < C < G < T, a prefix first); the
+ *   pointers stay valid until the next call on the handle. */
+typedef struct cfr_barcode cfr_barcode;
+typedef struct {
+  uint64_t whitelist_size;        /* distinct valid entries */
+  uint64_t table_slots;           /* slots of the device table, 0: host only */
+  uint64_t host_barcodes;         /* barcodes of the last count / correct call that went through the host twin */
+  uint64_t host_barcodes_total;   /* ... of all calls */
+  double device_ms;               /* stream time of the last call on the device: copies in, kernels, copies out */
+  int32_t barcode_length;         /* L, 0: mixed lengths (or no entry) */
+  int32_t on_device;
+} cfr_barcode_stats;
+cfr_status cfr_barcode_open(const char *whitelist_path, int device, cfr_barcode **out);
+cfr_status cfr_barcode_count(cfr_barcode *bc, const uint8_t *bases, const uint64_t *offsets, size_t n, size_t max_records);
+cfr_status cfr_barcode_correct(cfr_barcode *bc, const uint8_t *bases, const uint64_t *offsets, const char *qual, size_t n, int threads,
+                               int8_t *status, uint8_t *out_bases);
+cfr_status cfr_barcode_correct_host(cfr_barcode *bc, const uint8_t *bases, const uint64_t *offsets, const char *qual, size_t n, int threads,
+                                    int8_t *status, uint8_t *out_bases);
+cfr_status cfr_barcode_counts(cfr_barcode *bc, size_t *n_entries, const uint8_t **bases, const uint64_t **offsets, const uint32_t **counts);
+cfr_status cfr_barcode_get_stats(const cfr_barcode *bc, cfr_barcode_stats *st);
+void cfr_barcode_destroy(cfr_barcode *bc);
+
+/* cfr_barcode_translate_open: BarcodeTranslator::SetTranslateTable, lines `TO<sep>FROM` (sep: the first ',', tab or space).
+ * cfr_barcode_translate_apply: Translate per barcode - cut into len / from_len pieces, each looked up, joined with '-'.  status
+ *   (may be NULL): a barcode with status -1 becomes "N" and is not translated (CentrifugerClass.cpp:189-205).  Sizes first, bytes
+ *   second, as cfr_read_format_extract.  A piece that is not in the table: CFR_ERR_FORMAT, and cfr_last_error() is the reference's
+ *   "Barcode <piece> does not exist in the translation table." (it exits with status 255 there). */
+typedef struct cfr_barcode_translate cfr_barcode_translate;
+cfr_status cfr_barcode_translate_open(const char *path, cfr_barcode_translate **out);
+cfr_status cfr_barcode_translate_apply(const cfr_barcode_translate *t, const uint8_t *bases, const uint64_t *offsets, const int8_t *status,
+                                       size_t n, uint8_t *out_bases, uint64_t *out_offsets);
+void cfr_barcode_translate_destroy(cfr_barcode_translate *t);
+
+/* ResultWriter::OutputHeader / Output with the barcode and UMI columns (ResultWriter.hpp:186-242): they stand before
+ * expandedTaxIDs.  has_barcode / has_umi: the column is there; a NULL string prints a bare tab (PrintExtraCol).  With neither column
+ * the bytes are those of cfr_tsv_header / cfr_format_tsv (expanded = 0) or cfr_tsv_header_expanded / cfr_format_tsv_expanded. */
+const char *cfr_tsv_header_ex(int has_barcode, int has_umi, int expanded);
+size_t cfr_format_tsv_ex(const cfr_index *idx, const char *read_id, const cfr_result *r, const cfr_match *matches, int has_barcode,
+                         const char *barcode, int has_umi, const char *umi, int expanded, const cfr_span *spans, const uint64_t *ids,
+                         char *buf, size_t cap);
+
 /* ---- index writer (outside the classification path) ----
  * What `centrifuger-build` produces (Builder::Build + FMBuilder, Builder.hpp:86-313, compactds/FMBuilder.hpp:209-313):
  * <out_prefix>.{1,2,3,4}.cfr for nucleotide sequences, default layout options (--rbbwt-b / --offrate / --ftabchars
