@@ -1,6 +1,7 @@
 // cfr_barcode.cpp — host twins of ReadFormatter, BarcodeCorrector and BarcodeTranslator (see cfr_barcode.hpp for what is restated and
 // for the few places where the reference's behaviour is undefined), and the handle that chooses between the twin and the device table.
 #include "cfr_barcode.hpp"
+#include "cfr_threads.hpp"
 
 #include <zlib.h>
 
@@ -9,7 +10,6 @@
 #include <cstring>
 #include <functional>
 #include <stdexcept>
-#include <thread>
 
 namespace cfr {
 
@@ -377,8 +377,7 @@ void Barcode::correct(const uint8_t *bases, const uint64_t *offsets, const int8_
     sync_counts_to_host();
   }
   std::vector<uint64_t> to_host((size_t)threads, 0);
-  auto work = [&](int tid) {
-    const size_t lo = n * (size_t)tid / (size_t)threads, hi = n * (size_t)(tid + 1) / (size_t)threads;
+  parallel_slices(n, threads, [&](size_t lo, size_t hi, int tid) {
     if (hi > lo) memcpy(out_bases + offsets[lo], bases + offsets[lo], (size_t)(offsets[hi] - offsets[lo]));
     for (size_t i = lo; i < hi; ++i) {
       const uint64_t a = offsets[i];
@@ -393,13 +392,7 @@ void Barcode::correct(const uint8_t *bases, const uint64_t *offsets, const int8_
         ++to_host[(size_t)tid];
       }
     }
-  };
-  if (threads == 1) work(0);
-  else {
-    std::vector<std::thread> th;
-    for (int t = 0; t < threads; ++t) th.emplace_back(work, t);
-    for (auto &x : th) x.join();
-  }
+  });
   for (uint64_t v : to_host) host_barcodes += v;
   host_barcodes_total += host_barcodes;
 }

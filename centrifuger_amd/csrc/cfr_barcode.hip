@@ -28,26 +28,14 @@
 #include <cstring>
 
 #include "cfr_barcode.hpp"
-#include "cfr_device.hpp"
+#include "cfr_hip_util.hpp"
 
 namespace cfr {
 
 namespace {
 
-inline void hip_check(hipError_t e, const char *what) {
-  if (e != hipSuccess) throw HipError{std::string(what) + ": " + hipGetErrorString(e), (int)e};
-}
-#define HIP_CHECK(x) hip_check((x), #x)
-
-struct DeviceScope {
-  int prev = -1;
-  explicit DeviceScope(int d) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; HIP_CHECK(hipSetDevice(d)); }
-  ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
-inline unsigned grid_for(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 struct alignas(16) BcSlot { unsigned long long key; uint32_t count; uint32_t pad; };
 
@@ -174,32 +162,15 @@ __global__ __launch_bounds__(kBlock) void k_bc_correct(const BcSlot *table, uint
   }
 }
 
-template <class T> T *dmalloc(size_t n) {
-  void *p = nullptr;
-  HIP_CHECK(hipMalloc(&p, std::max<size_t>(n * sizeof(T), 16)));
-  return (T *)p;
-}
-
 class DeviceWhitelist : public BarcodeDevice {
  public:
   DeviceWhitelist(int device, int L, const std::vector<uint8_t> &bases, const std::vector<uint64_t> &offsets, const std::vector<uint32_t> &counts)
       : device_(device), L_(L), n_entries_(counts.size()) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) throw HipError{"cfr_barcode: no HIP device " + std::to_string(device), -1};
+    if (!device_exists(device)) throw HipError{"cfr_barcode: no HIP device " + std::to_string(device), -1};
     DeviceScope scope(device);
-    try { build(L, bases, offsets, counts); } catch (...) { release(); throw; }   // (no destructor runs for a constructor that throws)
-  }
-  ~DeviceWhitelist() override {
-    (void)hipSetDevice(device_);
-    if (stream_) (void)hipStreamSynchronize(stream_);
-    release();
-  }
-
- private:
-  void build(int L, const std::vector<uint8_t> &bases, const std::vector<uint64_t> &offsets, const std::vector<uint32_t> &counts) {
-    HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    HIP_CHECK(hipEventCreate(&ev0_));
-    HIP_CHECK(hipEventCreate(&ev1_));
+    stream_.create();
+    ev0_.create();
+    ev1_.create();
     slots_ = 64;
     while (slots_ < 2 * n_entries_) slots_ <<= 1;
     std::vector<unsigned long long> keys(n_entries_);
@@ -211,36 +182,30 @@ class DeviceWhitelist : public BarcodeDevice {
       }
       keys[e] = k;
     }
-    table_ = dmalloc<BcSlot>(slots_);
-    d_keys_ = dmalloc<unsigned long long>(n_entries_);
-    d_counts_ = dmalloc<uint32_t>(n_entries_);
+    table_.alloc(slots_);
+    d_keys_.alloc(n_entries_);
+    d_counts_.alloc(n_entries_);
     HIP_CHECK(hipMemsetAsync(table_, 0, slots_ * sizeof(BcSlot), stream_));
     if (n_entries_) {
       HIP_CHECK(hipMemcpyAsync(d_keys_, keys.data(), n_entries_ * 8, hipMemcpyHostToDevice, stream_));
       HIP_CHECK(hipMemcpyAsync(d_counts_, counts.data(), n_entries_ * 4, hipMemcpyHostToDevice, stream_));
-      hipLaunchKernelGGL(k_bc_build, dim3(grid_for(n_entries_)), dim3(kBlock), 0, stream_, table_, slots_ - 1, (const unsigned long long *)d_keys_,
+      hipLaunchKernelGGL(k_bc_build, dim3(grid_for(n_entries_)), dim3(kBlock), 0, stream_, table_.get(), slots_ - 1, (const unsigned long long *)d_keys_,
                          (const uint32_t *)d_counts_, n_entries_);
       HIP_CHECK(hipGetLastError());
     }
     HIP_CHECK(hipStreamSynchronize(stream_));   // (keys is a local)
   }
-  void release() {
-    for (void *p : {(void *)table_, (void *)d_keys_, (void *)d_counts_, (void *)d_bases_, (void *)d_qual_, (void *)d_off_, (void *)d_status_, (void *)d_pos_, (void *)d_base_})
-      if (p) (void)hipFree(p);
-    table_ = nullptr; d_keys_ = nullptr; d_counts_ = nullptr; d_bases_ = d_pos_ = d_base_ = nullptr; d_qual_ = d_status_ = nullptr; d_off_ = nullptr;
-    if (ev0_) (void)hipEventDestroy(ev0_);
-    if (ev1_) (void)hipEventDestroy(ev1_);
-    if (stream_) (void)hipStreamDestroy(stream_);
-    ev0_ = ev1_ = nullptr; stream_ = nullptr;
+  ~DeviceWhitelist() override {
+    (void)hipSetDevice(device_);
+    if (stream_) (void)hipStreamSynchronize(stream_);
   }
 
- public:
   void count(const uint8_t *bases, const uint64_t *offsets, size_t n) override {
     if (n == 0) { last_ms = 0; return; }
     DeviceScope scope(device_);
     HIP_CHECK(hipEventRecord(ev0_, stream_));
     upload(bases, offsets, nullptr, n);
-    hipLaunchKernelGGL(k_bc_count, dim3(grid_for(n)), dim3(kBlock), 0, stream_, table_, slots_ - 1, L_, (const uint8_t *)d_bases_, (const uint64_t *)d_off_, (uint64_t)n);
+    hipLaunchKernelGGL(k_bc_count, dim3(grid_for(n)), dim3(kBlock), 0, stream_, table_.get(), slots_ - 1, L_, (const uint8_t *)d_bases_, (const uint64_t *)d_off_, (uint64_t)n);
     HIP_CHECK(hipGetLastError());
     finish();
   }
@@ -251,7 +216,7 @@ class DeviceWhitelist : public BarcodeDevice {
     HIP_CHECK(hipEventRecord(ev0_, stream_));
     upload(bases, offsets, qual, n);
     hipLaunchKernelGGL(k_bc_correct, dim3(grid_for(n)), dim3(kBlock), 0, stream_, (const BcSlot *)table_, slots_ - 1, L_, (const uint8_t *)d_bases_,
-                       (const uint64_t *)d_off_, (const int8_t *)(qual ? d_qual_ : nullptr), (uint64_t)n, d_status_, d_pos_, d_base_);
+                       (const uint64_t *)d_off_, (const int8_t *)(qual ? d_qual_.get() : nullptr), (uint64_t)n, d_status_.get(), d_pos_.get(), d_base_.get());
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(status, d_status_, n, hipMemcpyDeviceToHost, stream_));
     HIP_CHECK(hipMemcpyAsync(pos, d_pos_, n, hipMemcpyDeviceToHost, stream_));
@@ -264,7 +229,7 @@ class DeviceWhitelist : public BarcodeDevice {
     if (!n_entries_) return;
     DeviceScope scope(device_);
     hipLaunchKernelGGL(k_bc_lookup, dim3(grid_for(n_entries_)), dim3(kBlock), 0, stream_, (const BcSlot *)table_, slots_ - 1, (const unsigned long long *)d_keys_,
-                       n_entries_, d_counts_);
+                       n_entries_, d_counts_.get());
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(counts.data(), d_counts_, n_entries_ * 4, hipMemcpyDeviceToHost, stream_));
     HIP_CHECK(hipStreamSynchronize(stream_));
@@ -273,23 +238,20 @@ class DeviceWhitelist : public BarcodeDevice {
   uint64_t table_slots() const override { return slots_; }
 
  private:
-  // the barcodes of one call: the bytes offsets[0] .. offsets[n) and the n + 1 offsets, rebased to the first byte
+  // the barcodes of one call: the bytes offsets[0] .. offsets[n) and the n + 1 offsets, rebased to the first byte.  A size class grows
+  // into fresh buffers that replace the old ones only when all of them exist.
   void upload(const uint8_t *bases, const uint64_t *offsets, const int8_t *qual, size_t n) {
     const uint64_t first = offsets[0], total = offsets[n] - first;
     if (total > cap_bytes_) {
-      if (d_bases_) { HIP_CHECK(hipFree(d_bases_)); d_bases_ = nullptr; }
-      if (d_qual_) { HIP_CHECK(hipFree(d_qual_)); d_qual_ = nullptr; }
-      cap_bytes_ = 0;
-      d_bases_ = dmalloc<uint8_t>(total);
-      cap_bytes_ = total;
+      DevBuf<uint8_t> b(total);
+      d_bases_ = std::move(b); d_qual_.reset(); cap_bytes_ = total;      // the qualities follow the bases' size, when they are asked for
     }
-    if (qual && !d_qual_) d_qual_ = dmalloc<int8_t>(cap_bytes_);
+    if (qual && !d_qual_) d_qual_.alloc(cap_bytes_);
     if (n > cap_n_) {
-      for (void *p : {(void *)d_off_, (void *)d_status_, (void *)d_pos_, (void *)d_base_}) if (p) HIP_CHECK(hipFree(p));
-      d_off_ = nullptr; d_status_ = nullptr; d_pos_ = d_base_ = nullptr; cap_n_ = 0;
-      d_off_ = dmalloc<uint64_t>(n + 1);
-      d_status_ = dmalloc<int8_t>(n); d_pos_ = dmalloc<uint8_t>(n); d_base_ = dmalloc<uint8_t>(n);
-      cap_n_ = n;
+      DevBuf<uint64_t> off(n + 1);
+      DevBuf<int8_t> st(n);
+      DevBuf<uint8_t> pos(n), base(n);
+      d_off_ = std::move(off); d_status_ = std::move(st); d_pos_ = std::move(pos); d_base_ = std::move(base); cap_n_ = n;
     }
     const uint64_t *src = offsets;
     if (first) {
@@ -311,14 +273,14 @@ class DeviceWhitelist : public BarcodeDevice {
 
   int device_, L_;
   uint64_t n_entries_, slots_ = 0;
-  hipStream_t stream_ = nullptr;
-  hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
-  BcSlot *table_ = nullptr;
-  unsigned long long *d_keys_ = nullptr;
-  uint32_t *d_counts_ = nullptr;
-  uint8_t *d_bases_ = nullptr, *d_pos_ = nullptr, *d_base_ = nullptr;
-  int8_t *d_qual_ = nullptr, *d_status_ = nullptr;
-  uint64_t *d_off_ = nullptr;
+  Stream stream_;                  // first: the last to go
+  Event ev0_, ev1_;
+  DevBuf<BcSlot> table_;
+  DevBuf<unsigned long long> d_keys_;
+  DevBuf<uint32_t> d_counts_;
+  DevBuf<uint8_t> d_bases_, d_pos_, d_base_;
+  DevBuf<int8_t> d_qual_, d_status_;
+  DevBuf<uint64_t> d_off_;
   uint64_t cap_bytes_ = 0;
   size_t cap_n_ = 0;
   std::vector<uint64_t> rebased_;

@@ -21,6 +21,7 @@
 #include <thread>
 
 #include "cfr_index.hpp"     // IoError
+#include "cfr_threads.hpp"
 
 namespace cfr {
 namespace {
@@ -401,9 +402,7 @@ void build_protein_index_files(const BuildInput &in, const BuildOptions &opt, co
     struct Run { uint64_t key = ~0ull, first = 0, count = 0; };
     std::vector<Run> head((size_t)threads), tail((size_t)threads);
     std::vector<uint64_t> fi((size_t)threads, ~0ull);
-    std::vector<std::thread> th;
-    for (int t = 0; t < threads; ++t) th.emplace_back([&, t]() {
-      const uint64_t lo = n * (uint64_t)t / (uint64_t)threads, hi = n * (uint64_t)(t + 1) / (uint64_t)threads;
+    parallel_slices(n, threads, [&](size_t lo, size_t hi, int t) {
       Run cur;
       bool first_run = true;
       auto flush = [&](bool last) {
@@ -427,7 +426,6 @@ void build_protein_index_files(const BuildInput &in, const BuildOptions &opt, co
       }
       flush(true);
     });
-    for (auto &x : th) x.join();
     for (int t = 0; t < threads; ++t) {
       if (fi[(size_t)t] != ~0ull) first_isa = fi[(size_t)t];
       for (const Run *r : {&head[(size_t)t], &tail[(size_t)t]}) if (r->key != ~0ull) {
@@ -589,14 +587,11 @@ void build_index_files(const BuildInput &in, const BuildOptions &opt, const std:
   uint64_t C[5] = {0, 0, 0, 0, 0};
   {
     std::vector<std::array<uint64_t, 4>> part((size_t)threads, std::array<uint64_t, 4>{0, 0, 0, 0});
-    std::vector<std::thread> th;
-    for (int t = 0; t < threads; ++t) th.emplace_back([&, t]() {
-      const uint64_t lo = n * (uint64_t)t / (uint64_t)threads, hi = n * (uint64_t)(t + 1) / (uint64_t)threads;
+    parallel_slices(n, threads, [&](size_t lo, size_t hi, int t) {
       uint64_t c[4] = {0, 0, 0, 0};
       for (uint64_t i = lo; i < hi; ++i) ++c[B[i]];
       for (int k = 0; k < 4; ++k) part[(size_t)t][(size_t)k] = c[k];
     });
-    for (auto &x : th) x.join();
     uint64_t cnt[4] = {0, 0, 0, 0};
     for (auto &p : part) for (int k = 0; k < 4; ++k) cnt[k] += p[(size_t)k];
     for (int k = 0; k < 4; ++k) C[k + 1] = C[k] + cnt[k];
@@ -611,10 +606,8 @@ void build_index_files(const BuildInput &in, const BuildOptions &opt, const std:
   const int parts_n = (int)std::min<uint64_t>((uint64_t)threads, std::max<uint64_t>(1, nblk / 4096));
   std::vector<Part> parts((size_t)parts_n);
   {
-    std::vector<std::thread> th;
-    for (int t = 0; t < parts_n; ++t) th.emplace_back([&, t]() {
+    parallel_slices(nblk, parts_n, [&](size_t blo, size_t bhi, int t) {
       Part &P = parts[(size_t)t];
-      const uint64_t blo = nblk * (uint64_t)t / (uint64_t)parts_n, bhi = nblk * (uint64_t)(t + 1) / (uint64_t)parts_n;
       auto push_sym = [](Wavelet &W, uint32_t s) { W.root.push(s >> 1); if (s >> 1) W.lo1.push(s & 1u); else W.lo0.push(s & 1u); ++W.n; };
       for (uint64_t k = blo; k < bhi; ++k) {
         const uint64_t st = k * b, end = std::min(st + b, n);          // the last block is judged on its real symbols only
@@ -625,7 +618,6 @@ void build_index_files(const BuildInput &in, const BuildOptions &opt, const std:
         else for (uint64_t q = st; q < end; ++q) push_sym(P.plain, B[q]);
       }
     });
-    for (auto &x : th) x.join();
   }
   Bits use;
   Wavelet plain, runs;

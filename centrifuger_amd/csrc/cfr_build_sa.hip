@@ -31,15 +31,11 @@
 #include <cstring>
 #include <memory>
 
-#include "cfr_device.hpp"      // HipError
+#define CFR_HIP_PREFIX "index build: "      // every HIP error of this file begins with it
+#include "cfr_hip_util.hpp"
 
 namespace cfr {
 namespace {
-
-inline void hip_check_b(hipError_t e, const char *what) {
-  if (e != hipSuccess) throw HipError{std::string("index build: ") + what + ": " + hipGetErrorString(e), (int)e};
-}
-#define BCHECK(x) hip_check_b((x), #x)
 
 struct __attribute__((packed)) U40b { uint32_t lo; uint8_t hi; };
 __device__ __forceinline__ void put40(uint8_t *tab, uint64_t i, uint64_t val) {
@@ -238,19 +234,7 @@ __global__ void k_ftab_finish(uint64_t entries, const unsigned long long *first,
   ftab[2 * k + 1] = count[k];
 }
 
-struct DevBuf {      // frees on scope exit, also when a HIP call throws
-  void *p = nullptr;
-  DevBuf() = default;
-  explicit DevBuf(size_t bytes) { BCHECK(hipMalloc(&p, bytes ? bytes : 16)); }
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  void alloc(size_t bytes) { release(); BCHECK(hipMalloc(&p, bytes ? bytes : 16)); }
-  void release() { if (p) (void)hipFree(p); p = nullptr; }
-  ~DevBuf() { release(); }
-  template <class T> T *as() const { return (T *)p; }
-};
-
-inline unsigned grid_of(uint64_t n, unsigned block = 256) { return (unsigned)std::max<uint64_t>(1, (n + block - 1) / block); }
+inline unsigned grid_of(uint64_t n) { return std::max(1u, grid_for(n)); }      // (a launch of no blocks is an error; the kernels check their index)
 
 }  // namespace
 
@@ -268,7 +252,7 @@ void build_sa_products(const uint8_t *text, uint64_t n, int device, uint32_t sam
     if (n + (limit >> 9) >= limit) throw HipError{"index build: texts of 2^36 symbols and more are beyond this single-GPU writer", -2};
   }
   if (w < 1 || w > 16) throw HipError{"index build: ftab width must be in 1..16", -2};
-  BCHECK(hipSetDevice(device));
+  HIP_CHECK(hipSetDevice(device));
   hipStream_t st = nullptr;      // default stream: everything here is sequential
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
@@ -277,22 +261,23 @@ void build_sa_products(const uint8_t *text, uint64_t n, int device, uint32_t sam
 
   // ---- text
   const uint64_t nwords = (n + 31) / 32;
-  DevBuf d_text((nwords + 4) * 8);
-  uint64_t *T = d_text.as<uint64_t>();
-  BCHECK(hipMemsetAsync(T, 0, (nwords + 4) * 8, st));
+  DevBuf<uint64_t> d_text(nwords + 4);
+  uint64_t *T = d_text;
+  HIP_CHECK(hipMemsetAsync(T, 0, (nwords + 4) * 8, st));
   {
     const uint64_t piece = 1ull << 30;
-    DevBuf stage(piece), d_bad(4);
-    BCHECK(hipMemsetAsync(d_bad.p, 0, 4, st));
+    DevBuf<uint8_t> stage(piece);
+    DevBuf<unsigned int> d_bad(1);
+    HIP_CHECK(hipMemsetAsync(d_bad, 0, 4, st));
     for (uint64_t lo = 0; lo < n; lo += piece) {
       const uint64_t cnt = std::min(piece, n - lo);
-      BCHECK(hipMemcpy(stage.p, text + lo, cnt, hipMemcpyHostToDevice));
-      k_pack_text<<<grid_of((cnt + 31) / 32), 256, 0, st>>>(stage.as<uint8_t>(), cnt, T + lo / 32, d_bad.as<unsigned int>());
-      BCHECK(hipGetLastError());
-      BCHECK(hipStreamSynchronize(st));
+      HIP_CHECK(hipMemcpy(stage, text + lo, cnt, hipMemcpyHostToDevice));
+      k_pack_text<<<grid_of((cnt + 31) / 32), 256, 0, st>>>(stage.get(), cnt, T + lo / 32, d_bad.get());
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipStreamSynchronize(st));
     }
     unsigned int bad = 0;
-    BCHECK(hipMemcpy(&bad, d_bad.p, 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost));
     if (bad) throw HipError{"index build: the text must be upper-case ACGT only", -2};
   }
 
@@ -306,7 +291,7 @@ void build_sa_products(const uint8_t *text, uint64_t n, int device, uint32_t sam
   const uint64_t kMargin = std::min<uint64_t>(1ull << 20, kChunk / 2);      // a span ends on the first group boundary past chunk - margin
   // SA on the device when SA + RANK + text + head bits + chunk buffers fit, else in host memory (one chunk / span on the device)
   size_t free_b = 0, total_b = 0;
-  BCHECK(hipMemGetInfo(&free_b, &total_b));
+  HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
   const bool host_sa = (double)n * 10.2 + 16e9 > 0.95 * (double)free_b || (dbg && getenv("CFR_BUILD_HOST_SA") && atoi(getenv("CFR_BUILD_HOST_SA")));
   if (host_sa && (double)n * 5.2 + 22e9 > 0.95 * (double)free_b) throw HipError{"index build: the text does not fit this device even with the suffix array on the host", -3};
   std::unique_ptr<uint8_t[]> hsa_mem;       // (not a vector: 5 n bytes must not be zero-filled first)
@@ -316,43 +301,44 @@ void build_sa_products(const uint8_t *text, uint64_t n, int device, uint32_t sam
     hsa = hsa_mem.get();
     if (log) log("suffix array kept in host memory (" + std::to_string((n * 5) >> 30) + " GiB); RANK, text and head bits in HBM");
   }
-  DevBuf d_sa(host_sa ? kChunk * 5 + 16 : n * 5 + 16), d_rank(n * 5 + 16), d_head(((n + 1 + 63) / 64 + 2) * 8);
-  uint8_t *SA = d_sa.as<uint8_t>(), *RANK = d_rank.as<uint8_t>();
-  unsigned long long *HB = d_head.as<unsigned long long>();
-  BCHECK(hipMemsetAsync(HB, 0, ((n + 1 + 63) / 64 + 2) * 8, st));
+  DevBuf<uint8_t> d_sa(host_sa ? kChunk * 5 + 16 : n * 5 + 16), d_rank(n * 5 + 16);
+  DevBuf<unsigned long long> d_head((n + 1 + 63) / 64 + 2);
+  uint8_t *SA = d_sa, *RANK = d_rank;
+  unsigned long long *HB = d_head;
+  HIP_CHECK(hipMemsetAsync(HB, 0, ((n + 1 + 63) / 64 + 2) * 8, st));
 
   // chunk buffers (shared by both phases)
-  DevBuf bK0(kChunk * 8), bK1(kChunk * 8), bP0(kChunk * 8), bP1(kChunk * 8), bSlots(kChunk * 8), bHS(kChunk * 8), bGrp(kChunk * 8), bScalar(64);
-  uint64_t *K0 = bK0.as<uint64_t>(), *K1 = bK1.as<uint64_t>(), *P0 = bP0.as<uint64_t>(), *P1 = bP1.as<uint64_t>();
-  uint64_t *SL = bSlots.as<uint64_t>(), *HS = bHS.as<uint64_t>(), *GRP = bGrp.as<uint64_t>();
-  unsigned long long *d_scalar = bScalar.as<unsigned long long>();
+  DevBuf<uint64_t> bK0(kChunk), bK1(kChunk), bP0(kChunk), bP1(kChunk), bSlots(kChunk), bHS(kChunk), bGrp(kChunk);
+  DevBuf<unsigned long long> bScalar(8);
+  uint64_t *K0 = bK0, *K1 = bK1, *P0 = bP0, *P1 = bP1, *SL = bSlots, *HS = bHS, *GRP = bGrp;
+  unsigned long long *d_scalar = bScalar;
   size_t tmp_sort = 0, tmp_scan = 0, tmp_sel = 0;
-  BCHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, K0, K1, P0, P1, (uint64_t)kChunk, 0, 64, st));
-  BCHECK(hipcub::DeviceScan::InclusiveScan(nullptr, tmp_scan, HS, GRP, MaxOp(), (uint64_t)kChunk, st));
+  HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, K0, K1, P0, P1, (uint64_t)kChunk, 0, 64, st));
+  HIP_CHECK(hipcub::DeviceScan::InclusiveScan(nullptr, tmp_scan, HS, GRP, MaxOp(), (uint64_t)kChunk, st));
   {
     hipcub::CountingInputIterator<uint64_t> it(0);
-    BCHECK(hipcub::DeviceSelect::If(nullptr, tmp_sel, it, SL, (uint64_t *)d_scalar, (int)kChunk, ActivePred{HB}, st));
+    HIP_CHECK(hipcub::DeviceSelect::If(nullptr, tmp_sel, it, SL, (uint64_t *)d_scalar, (int)kChunk, ActivePred{HB}, st));
   }
   const size_t tmp_bytes = std::max(tmp_sort, std::max(tmp_scan, tmp_sel));
-  DevBuf bTmp(tmp_bytes);
+  DevBuf<uint8_t> bTmp(tmp_bytes);
 
   // sa_off: first row the SA buffer holds (0 with the whole array on the device)
   auto commit = [&](uint64_t *Ksorted, uint64_t *Psorted, uint64_t m, const uint64_t *slots, uint64_t slot_base, uint64_t sa_off) {
     k_new_heads<<<grid_of(m), 256, 0, st>>>(Ksorted, m, slots, slot_base, HS);
     size_t tb = tmp_bytes;
-    BCHECK(hipcub::DeviceScan::InclusiveScan(bTmp.p, tb, HS, GRP, MaxOp(), m, st));
+    HIP_CHECK(hipcub::DeviceScan::InclusiveScan(bTmp, tb, HS, GRP, MaxOp(), m, st));
     k_commit<<<grid_of(m), 256, 0, st>>>(Psorted, GRP, HS, m, slots, slot_base, SA, sa_off, RANK, HB);
-    BCHECK(hipGetLastError());
+    HIP_CHECK(hipGetLastError());
   };
 
   // ---- phase 1: order by the first 32 symbols
   {
-    DevBuf d_hist((1u << kBinBits) * 8);
-    BCHECK(hipMemsetAsync(d_hist.p, 0, (1u << kBinBits) * 8, st));
-    k_hist<<<2048, 256, 0, st>>>(T, n, d_hist.as<unsigned long long>());
-    BCHECK(hipGetLastError());
+    DevBuf<unsigned long long> d_hist(1u << kBinBits);
+    HIP_CHECK(hipMemsetAsync(d_hist, 0, (1u << kBinBits) * 8, st));
+    k_hist<<<2048, 256, 0, st>>>(T, n, d_hist.get());
+    HIP_CHECK(hipGetLastError());
     std::vector<unsigned long long> hist(1u << kBinBits);
-    BCHECK(hipMemcpy(hist.data(), d_hist.p, hist.size() * 8, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(hist.data(), d_hist, hist.size() * 8, hipMemcpyDeviceToHost));
     uint64_t base = 0;
     uint32_t bin = 0;
     int chunks = 0;
@@ -362,13 +348,13 @@ void build_sa_products(const uint8_t *text, uint64_t n, int device, uint32_t sam
       while (hi < (1u << kBinBits) && cnt + hist[hi] <= kChunk) cnt += hist[hi++];
       if (hi == bin) throw HipError{"index build: more suffixes than one chunk holds share one 7-symbol prefix (text too skewed for this writer)", -2};
       if (cnt) {
-        BCHECK(hipMemsetAsync(d_scalar, 0, 8, st));
+        HIP_CHECK(hipMemsetAsync(d_scalar, 0, 8, st));
         k_collect<<<4096, 256, 0, st>>>(T, n, bin, hi, d_scalar, K0, P0);
-        BCHECK(hipGetLastError());
+        HIP_CHECK(hipGetLastError());
         size_t tb = tmp_bytes;
-        BCHECK(hipcub::DeviceRadixSort::SortPairs(bTmp.p, tb, K0, K1, P0, P1, cnt, 0, 64, st));
+        HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(bTmp, tb, K0, K1, P0, P1, cnt, 0, 64, st));
         commit(K1, P1, cnt, nullptr, base, host_sa ? base : 0);
-        if (host_sa) BCHECK(hipMemcpy(hsa + base * 5, SA, cnt * 5, hipMemcpyDeviceToHost));
+        if (host_sa) HIP_CHECK(hipMemcpy(hsa + base * 5, SA, cnt * 5, hipMemcpyDeviceToHost));
         ++chunks;
       }
       base += cnt;
@@ -376,11 +362,11 @@ void build_sa_products(const uint8_t *text, uint64_t n, int device, uint32_t sam
     }
     if (base != n) throw HipError{"index build: internal error (phase 1 lost suffixes)", -5};
     const unsigned long long one = 1ull << (n & 63);                  // bit n: the end of the last group
-    BCHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipStreamSynchronize(st));
     unsigned long long last = 0;
-    BCHECK(hipMemcpy(&last, HB + (n >> 6), 8, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&last, HB + (n >> 6), 8, hipMemcpyDeviceToHost));
     last |= one;
-    BCHECK(hipMemcpy(HB + (n >> 6), &last, 8, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(HB + (n >> 6), &last, 8, hipMemcpyHostToDevice));
     snprintf(msg, sizeof(msg), "suffix array: %d chunks sorted by their first 32 symbols, %.1f s", chunks, secs(t_begin, now()));
     if (log) log(msg);
   }
@@ -395,30 +381,30 @@ void build_sa_products(const uint8_t *text, uint64_t n, int device, uint32_t sam
       uint64_t hi = n;
       if (n - lo > kChunk - kMargin) {      // a span ends on the first group boundary at or after lo + chunk - margin (groups are far smaller than the margin)
         k_next_head<<<1, 1, 0, st>>>(HB, lo + kChunk - kMargin, (uint64_t *)d_scalar + 1);
-        BCHECK(hipMemcpy(&hi, (uint64_t *)d_scalar + 1, 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(&hi, (uint64_t *)d_scalar + 1, 8, hipMemcpyDeviceToHost));
         if (hi - lo > kChunk) throw HipError{"index build: a group of more than 2^20 equal prefixes (text too repetitive for this writer)", -2};
       }
       hipcub::CountingInputIterator<uint64_t> it(lo);
       size_t tb = tmp_bytes;
-      BCHECK(hipcub::DeviceSelect::If(bTmp.p, tb, it, SL, (uint64_t *)d_scalar, (int)(hi - lo), ActivePred{HB}, st));
+      HIP_CHECK(hipcub::DeviceSelect::If(bTmp, tb, it, SL, (uint64_t *)d_scalar, (int)(hi - lo), ActivePred{HB}, st));
       uint64_t m = 0;
-      BCHECK(hipMemcpy(&m, d_scalar, 8, hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(&m, d_scalar, 8, hipMemcpyDeviceToHost));
       if (m) {
-        if (host_sa) BCHECK(hipMemcpy(SA, hsa + lo * 5, (hi - lo) * 5, hipMemcpyHostToDevice));
+        if (host_sa) HIP_CHECK(hipMemcpy(SA, hsa + lo * 5, (hi - lo) * 5, hipMemcpyHostToDevice));
         k_active_heads<<<grid_of(m), 256, 0, st>>>(HB, SL, m, HS);
         tb = tmp_bytes;
-        BCHECK(hipcub::DeviceScan::InclusiveScan(bTmp.p, tb, HS, GRP, MaxOp(), m, st));
+        HIP_CHECK(hipcub::DeviceScan::InclusiveScan(bTmp, tb, HS, GRP, MaxOp(), m, st));
         k_gather_keys<<<grid_of(m), 256, 0, st>>>(SA, host_sa ? lo : 0, RANK, SL, GRP, m, lo, n, h, rank_bits, K0, P0);
-        BCHECK(hipGetLastError());
+        HIP_CHECK(hipGetLastError());
         tb = tmp_bytes;
-        BCHECK(hipcub::DeviceRadixSort::SortPairs(bTmp.p, tb, K0, K1, P0, P1, m, 0, 64, st));
+        HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(bTmp, tb, K0, K1, P0, P1, m, 0, 64, st));
         commit(K1, P1, m, SL, 0, host_sa ? lo : 0);
-        if (host_sa) BCHECK(hipMemcpy(hsa + lo * 5, SA, (hi - lo) * 5, hipMemcpyDeviceToHost));
+        if (host_sa) HIP_CHECK(hipMemcpy(hsa + lo * 5, SA, (hi - lo) * 5, hipMemcpyDeviceToHost));
       }
       active_total += m;
       lo = hi;
     }
-    BCHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipStreamSynchronize(st));
     if (active_total == 0) break;
     ++rounds;
     snprintf(msg, sizeof(msg), "suffix array: round %d (depth %llu -> %llu): %llu rows in unresolved groups, %.1f s", rounds,
@@ -430,55 +416,57 @@ void build_sa_products(const uint8_t *text, uint64_t n, int device, uint32_t sam
   const auto t_prod = now();
 
   // ---- products
-  bK0.release(); bK1.release(); bP0.release(); bP1.release(); bSlots.release(); bHS.release(); bGrp.release(); bTmp.release();
+  bK0.reset(); bK1.reset(); bP0.reset(); bP1.reset(); bSlots.reset(); bHS.reset(); bGrp.reset(); bTmp.reset();
   out.n = n;
   out.rows_of.assign(want_pos.size(), 0);
   if (!want_pos.empty()) {
-    DevBuf d_want(want_pos.size() * 8), d_rows(want_pos.size() * 8);
-    BCHECK(hipMemcpy(d_want.p, want_pos.data(), want_pos.size() * 8, hipMemcpyHostToDevice));
-    k_rows_of<<<grid_of(want_pos.size()), 256, 0, st>>>(RANK, d_want.as<uint64_t>(), want_pos.size(), d_rows.as<uint64_t>());
-    BCHECK(hipGetLastError());
-    BCHECK(hipMemcpy(out.rows_of.data(), d_rows.p, want_pos.size() * 8, hipMemcpyDeviceToHost));
+    DevBuf<uint64_t> d_want(want_pos.size()), d_rows(want_pos.size());
+    HIP_CHECK(hipMemcpy(d_want, want_pos.data(), want_pos.size() * 8, hipMemcpyHostToDevice));
+    k_rows_of<<<grid_of(want_pos.size()), 256, 0, st>>>(RANK, d_want.get(), want_pos.size(), d_rows.get());
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpy(out.rows_of.data(), d_rows, want_pos.size() * 8, hipMemcpyDeviceToHost));
   }
-  d_rank.release();
-  d_head.release();
+  d_rank.reset();
+  d_head.reset();
   {
     // rows in pieces: the whole array when the SA is on the device, one chunk at a time from the host copy otherwise
     const uint64_t piece = host_sa ? kChunk : n;
     const uint64_t nsamp = (n + sample_rate - 1) / sample_rate, entries = 1ull << (2 * w);
-    DevBuf d_psum(psum.size() * 8), d_ids(std::min<uint64_t>(nsamp, piece / sample_rate + 2) * 4), d_first(entries * 8), d_count(entries * 8), d_ftab(entries * 16);
-    DevBuf d_bwt(piece), d_fi(8);
-    BCHECK(hipMemcpy(d_psum.p, psum.data(), psum.size() * 8, hipMemcpyHostToDevice));
-    BCHECK(hipMemsetAsync(d_first.p, 0xff, entries * 8, st));
-    BCHECK(hipMemsetAsync(d_count.p, 0, entries * 8, st));
-    BCHECK(hipMemsetAsync(d_fi.p, 0, 8, st));
+    DevBuf<uint64_t> d_psum(psum.size()), d_ftab(entries * 2);
+    DevBuf<uint32_t> d_ids(std::min<uint64_t>(nsamp, piece / sample_rate + 2));
+    DevBuf<unsigned long long> d_first(entries), d_count(entries), d_fi(1);
+    DevBuf<uint8_t> d_bwt(piece);
+    HIP_CHECK(hipMemcpy(d_psum, psum.data(), psum.size() * 8, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemsetAsync(d_first, 0xff, entries * 8, st));
+    HIP_CHECK(hipMemsetAsync(d_count, 0, entries * 8, st));
+    HIP_CHECK(hipMemsetAsync(d_fi, 0, 8, st));
     out.bwt.resize(n);
     std::vector<uint32_t> &ids = out.sampled_ids;
     ids.resize(nsamp);
     for (uint64_t lo = 0; lo < n; lo += piece) {
       const uint64_t hi = std::min(n, lo + piece), sa_off = host_sa ? lo : 0;
-      if (host_sa) BCHECK(hipMemcpy(SA, hsa + lo * 5, (hi - lo) * 5, hipMemcpyHostToDevice));
+      if (host_sa) HIP_CHECK(hipMemcpy(SA, hsa + lo * 5, (hi - lo) * 5, hipMemcpyHostToDevice));
       const uint64_t k_lo = (lo + sample_rate - 1) / sample_rate, k_hi = (hi + sample_rate - 1) / sample_rate;      // samples with row in [lo, hi)
       if (k_hi > k_lo) {
-        k_sampled<<<(unsigned)std::min<uint64_t>(grid_of(k_hi - k_lo), 1u << 20), 256, 0, st>>>(SA, sa_off, n, sample_rate, w, d_psum.as<uint64_t>(), psum.size() - 1, k_lo, k_hi, d_ids.as<uint32_t>());
-        BCHECK(hipGetLastError());
-        BCHECK(hipMemcpy(ids.data() + k_lo, d_ids.p, (k_hi - k_lo) * 4, hipMemcpyDeviceToHost));
+        k_sampled<<<(unsigned)std::min<uint64_t>(grid_of(k_hi - k_lo), 1u << 20), 256, 0, st>>>(SA, sa_off, n, sample_rate, w, d_psum.get(), psum.size() - 1, k_lo, k_hi, d_ids.get());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(ids.data() + k_lo, d_ids, (k_hi - k_lo) * 4, hipMemcpyDeviceToHost));
       }
-      k_ftab<<<grid_of((hi - lo + 255) / 256), 256, 0, st>>>(T, SA, sa_off, lo, hi, n, w, d_first.as<unsigned long long>(), d_count.as<unsigned long long>());
-      k_bwt<<<(unsigned)std::min<uint64_t>(grid_of(hi - lo), 1u << 20), 256, 0, st>>>(T, SA, sa_off, lo, hi, n, d_bwt.as<uint8_t>(), d_fi.as<unsigned long long>());
-      BCHECK(hipGetLastError());
-      BCHECK(hipMemcpy(out.bwt.data() + lo, d_bwt.p, hi - lo, hipMemcpyDeviceToHost));
+      k_ftab<<<grid_of((hi - lo + 255) / 256), 256, 0, st>>>(T, SA, sa_off, lo, hi, n, w, d_first.get(), d_count.get());
+      k_bwt<<<(unsigned)std::min<uint64_t>(grid_of(hi - lo), 1u << 20), 256, 0, st>>>(T, SA, sa_off, lo, hi, n, d_bwt.get(), d_fi.get());
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipMemcpy(out.bwt.data() + lo, d_bwt, hi - lo, hipMemcpyDeviceToHost));
       if (host_sa) {      // this piece of the host copy is done with: give its pages back while the BWT grows
         const uintptr_t a0 = ((uintptr_t)(hsa + lo * 5) + 4095) & ~(uintptr_t)4095, a1 = (uintptr_t)(hsa + hi * 5) & ~(uintptr_t)4095;
         if (a1 > a0) (void)madvise((void *)a0, a1 - a0, MADV_DONTNEED);
       }
     }
-    k_ftab_finish<<<grid_of(entries), 256, 0, st>>>(entries, d_first.as<unsigned long long>(), d_count.as<unsigned long long>(), d_ftab.as<uint64_t>());
-    BCHECK(hipGetLastError());
+    k_ftab_finish<<<grid_of(entries), 256, 0, st>>>(entries, d_first.get(), d_count.get(), d_ftab.get());
+    HIP_CHECK(hipGetLastError());
     out.ftab.resize(entries * 2);
-    BCHECK(hipMemcpy(out.ftab.data(), d_ftab.p, entries * 16, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(out.ftab.data(), d_ftab, entries * 16, hipMemcpyDeviceToHost));
     unsigned long long fi = 0;
-    BCHECK(hipMemcpy(&fi, d_fi.p, 8, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&fi, d_fi, 8, hipMemcpyDeviceToHost));
     out.first_isa = fi;
   }
   out.seconds_products = secs(t_prod, now());
@@ -523,46 +511,48 @@ void build_sa_bytes(const uint8_t *codes, uint64_t n, int device, std::vector<ui
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw HipError{"index build: no HIP device (the writer has no CPU path)", -1};
   if (device < 0 || device >= count) throw HipError{"index build: device ordinal out of range", -1};
   if (n == 0 || n >= 0xfffffff0ull) throw HipError{"index build: a byte text must hold between 1 and 2^32 - 16 symbols", -2};
-  BCHECK(hipSetDevice(device));
+  HIP_CHECK(hipSetDevice(device));
   hipStream_t st = nullptr;
   const auto t_begin = std::chrono::steady_clock::now();
-  DevBuf d_text(n + 16), bK0(n * 8), bK1(n * 8), bP0(n * 4), bP1(n * 4), bRank(n * 4), bFlag(n * 4), bGrp(n * 4);
-  BCHECK(hipMemcpy(d_text.p, codes, n, hipMemcpyHostToDevice));
-  uint64_t *K0 = bK0.as<uint64_t>(), *K1 = bK1.as<uint64_t>();
-  uint32_t *P0 = bP0.as<uint32_t>(), *P1 = bP1.as<uint32_t>(), *RANK = bRank.as<uint32_t>(), *FLAG = bFlag.as<uint32_t>(), *GRP = bGrp.as<uint32_t>();
+  DevBuf<uint8_t> d_text(n + 16);
+  DevBuf<uint64_t> bK0(n), bK1(n);
+  DevBuf<uint32_t> bP0(n), bP1(n), bRank(n), bFlag(n), bGrp(n);
+  HIP_CHECK(hipMemcpy(d_text, codes, n, hipMemcpyHostToDevice));
+  uint64_t *K0 = bK0, *K1 = bK1;
+  uint32_t *P0 = bP0, *P1 = bP1, *RANK = bRank, *FLAG = bFlag, *GRP = bGrp;
   size_t tmp_sort = 0, tmp_scan = 0;
-  BCHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, K0, K1, P0, P1, n, 0, 64, st));
-  BCHECK(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_scan, FLAG, GRP, n, st));
+  HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, K0, K1, P0, P1, n, 0, 64, st));
+  HIP_CHECK(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_scan, FLAG, GRP, n, st));
   size_t tmp_bytes = std::max(tmp_sort, tmp_scan);
-  DevBuf bTmp(tmp_bytes);
+  DevBuf<uint8_t> bTmp(tmp_bytes);
   const unsigned grid = (unsigned)std::min<uint64_t>(grid_of(n), 1u << 16);
   uint32_t groups = 0;
   int round = 0;
   auto renumber = [&](int end_bit) {        // K0 / P0 hold the keys by position: sort, number the groups, hand every position its group
     size_t tb = tmp_bytes;
-    BCHECK(hipcub::DeviceRadixSort::SortPairs(bTmp.p, tb, K0, K1, P0, P1, n, 0, end_bit, st));
+    HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(bTmp, tb, K0, K1, P0, P1, n, 0, end_bit, st));
     k_bytes_flags<<<grid, 256, 0, st>>>(K1, n, FLAG);
-    BCHECK(hipGetLastError());
+    HIP_CHECK(hipGetLastError());
     tb = tmp_bytes;
-    BCHECK(hipcub::DeviceScan::InclusiveSum(bTmp.p, tb, FLAG, GRP, n, st));
+    HIP_CHECK(hipcub::DeviceScan::InclusiveSum(bTmp, tb, FLAG, GRP, n, st));
     k_bytes_scatter<<<grid, 256, 0, st>>>(P1, GRP, n, RANK);
-    BCHECK(hipGetLastError());
-    BCHECK(hipMemcpy(&groups, GRP + (n - 1), 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpy(&groups, GRP + (n - 1), 4, hipMemcpyDeviceToHost));
     ++round;
   };
-  k_bytes_key0<<<grid, 256, 0, st>>>(d_text.as<uint8_t>(), n, K0, P0);
-  BCHECK(hipGetLastError());
+  k_bytes_key0<<<grid, 256, 0, st>>>(d_text.get(), n, K0, P0);
+  HIP_CHECK(hipGetLastError());
   renumber(60);
   uint64_t h = 12;
   while ((uint64_t)groups < n) {
     if (h >= 2 * n + 24) throw HipError{"index build: the doubling rounds of a byte text did not separate its suffixes", -3};
     k_bytes_key_h<<<grid, 256, 0, st>>>(RANK, n, h, K0, P0);
-    BCHECK(hipGetLastError());
+    HIP_CHECK(hipGetLastError());
     renumber(64);
     h *= 2;
   }
   sa.resize(n);
-  BCHECK(hipMemcpy(sa.data(), P1, n * 4, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(sa.data(), P1, n * 4, hipMemcpyDeviceToHost));
   if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
   if (rounds) *rounds = round;
 }

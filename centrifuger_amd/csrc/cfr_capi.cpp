@@ -18,6 +18,7 @@
 #include "cfr_device.hpp"
 #include "cfr_quant.hpp"
 #include "cfr_tail.hpp"
+#include "cfr_threads.hpp"
 
 struct cfr_index { cfr::HostIndex *h; };
 struct cfr_read_format { cfr::ReadFormat f; };
@@ -339,7 +340,6 @@ cfr_status cfr_classify_batch_expanded(cfr_dev_index *d, const uint8_t *bases1, 
 cfr_status cfr_pack_reads(const uint8_t *bases, uint64_t total, int threads, uint64_t *packed) {
   if ((total && !bases) || !packed) return bad_arg("cfr_pack_reads: null argument");
   const uint64_t nblk = (total + 15) / 16;
-  if (threads < 1) threads = 1;
   auto conv4 = [](uint32_t x, uint32_t &code8, uint32_t &valid4) {        // 4 ASCII bytes -> 4 two-bit codes + 4 validity bits (the device's conv4)
     uint32_t k = (x >> 1) & 0x03030303u;
     k ^= (k >> 1) & 0x01010101u;
@@ -351,8 +351,7 @@ cfr_status cfr_pack_reads(const uint8_t *bases, uint64_t total, int threads, uin
     valid4 = ((ok >> 7) | (ok >> 14) | (ok >> 21) | (ok >> 28)) & 0xfu;
     code8 = (k | (k >> 6) | (k >> 12) | (k >> 18)) & 0xffu;
   };
-  auto work = [&](int tid) {
-    const uint64_t lo = nblk * (uint64_t)tid / (uint64_t)threads, hi = nblk * (uint64_t)(tid + 1) / (uint64_t)threads;
+  cfr::parallel_slices(nblk, nblk < 4096 ? 1 : threads, [&](size_t lo, size_t hi, int) {
     for (uint64_t b = lo; b < hi; ++b) {
       uint32_t w[4] = {0, 0, 0, 0};
       const uint64_t a = b << 4;
@@ -362,13 +361,7 @@ cfr_status cfr_pack_reads(const uint8_t *bases, uint64_t total, int threads, uin
       for (int q = 0; q < 4; ++q) { uint32_t c8, v4; conv4(w[q], c8, v4); c |= c8 << (8 * q); vv |= v4 << (4 * q); }
       packed[b] = (uint64_t)c | ((uint64_t)vv << 32);
     }
-  };
-  if (threads == 1 || nblk < 4096) { threads = 1; work(0); }
-  else {
-    std::vector<std::thread> th;
-    for (int t = 0; t < threads; ++t) th.emplace_back(work, t);
-    for (auto &x : th) x.join();
-  }
+  });
   return CFR_OK;
 }
 
@@ -523,18 +516,10 @@ cfr_status cfr_last_batch_stats(const cfr_dev_index *d, cfr_batch_stats *st) {
 
 static cfr_status dust_batch(uint8_t *bases, const uint64_t *offsets, size_t n, int threads, void (*mask)(uint8_t *, size_t)) {
   if (n && (!bases || !offsets)) return bad_arg("cfr_dust_mask_batch: null argument");
-  if (threads < 1) threads = 1;
-  auto work = [&](int tid) {
-    // a contiguous slice per thread (reads are independent; the reference strides them, the result is the same)
-    const size_t lo = n * (size_t)tid / (size_t)threads, hi = n * (size_t)(tid + 1) / (size_t)threads;
+  // a contiguous slice per thread (reads are independent; the reference strides them, the result is the same)
+  cfr::parallel_slices(n, threads, [&](size_t lo, size_t hi, int) {
     for (size_t i = lo; i < hi; ++i) mask(bases + offsets[i], offsets[i + 1] - offsets[i]);
-  };
-  if (threads == 1) work(0);
-  else {
-    std::vector<std::thread> th;
-    for (int t = 0; t < threads; ++t) th.emplace_back(work, t);
-    for (auto &x : th) x.join();
-  }
+  });
   return CFR_OK;
 }
 cfr_status cfr_dust_mask_batch(uint8_t *bases, const uint64_t *offsets, size_t n, int threads) {
@@ -840,14 +825,7 @@ cfr_status cfr_merge_pairs(const uint8_t *bases1, const uint64_t *offsets1, cons
   std::vector<uint64_t> at(n, 0);
   std::vector<std::vector<uint8_t>> mb((size_t)threads);
   std::vector<std::vector<int8_t>> mq((size_t)threads);
-  auto run = [&](const std::function<void(int)> &f) {
-    if (threads == 1) { f(0); return; }
-    std::vector<std::thread> th;
-    for (int t = 0; t < threads; ++t) th.emplace_back(f, t);
-    for (auto &x : th) x.join();
-  };
-  run([&](int tid) {
-    const size_t lo = n * (size_t)tid / (size_t)threads, hi = n * (size_t)(tid + 1) / (size_t)threads;
+  cfr::parallel_slices(n, threads, [&](size_t lo, size_t hi, int tid) {
     cfr::MergeScratch ws;
     std::vector<uint8_t> rm;
     std::vector<int8_t> qm;
@@ -874,8 +852,7 @@ cfr_status cfr_merge_pairs(const uint8_t *bases1, const uint64_t *offsets1, cons
   });
   out_offsets1[0] = out_offsets2[0] = 0;
   for (size_t i = 0; i < n; ++i) { out_offsets1[i + 1] += out_offsets1[i]; out_offsets2[i + 1] += out_offsets2[i]; }
-  run([&](int tid) {
-    const size_t lo = n * (size_t)tid / (size_t)threads, hi = n * (size_t)(tid + 1) / (size_t)threads;
+  cfr::parallel_slices(n, threads, [&](size_t lo, size_t hi, int tid) {
     for (size_t i = lo; i < hi; ++i) {
       const uint64_t d1 = out_offsets1[i], m1 = out_offsets1[i + 1] - d1, d2 = out_offsets2[i], m2 = out_offsets2[i + 1] - d2;
       if (kd[i]) {

@@ -12,17 +12,13 @@
 #include <thread>
 #include <type_traits>
 
+#include "cfr_hip_util.hpp"
 #include "cfr_tail.hpp"      // dust_mask: the host twin the device SDUST falls back to
 #include "cfr_kernels.hip.inc"
 
 namespace cfr {
 
 namespace {
-
-inline void hip_check(hipError_t e, const char *what) {
-  if (e != hipSuccess) throw HipError{std::string(what) + ": " + hipGetErrorString(e), (int)e};
-}
-#define HIP_CHECK(x) hip_check((x), #x)
 
 // The CFR_* switches of profiles/HISTORY.md section 5 are A/B and test hooks, not part of the library's interface: they are only
 // looked at when CFR_DEBUG_ENV=1 is set in the environment (one documented gate; a production caller never sets it and
@@ -34,7 +30,6 @@ inline const char *dbg_env(const char *name) {
 
 constexpr int kBlock = 256;
 constexpr size_t kCtlWords = 4;      // words of a sub-batch's control block the host reads back: pool overflow, reads folded by small / large teams, reads left to k_adjust_tail
-inline unsigned grid_for(size_t n, int block = kBlock) { return (unsigned)((n + block - 1) / block); }
 
 enum Slot : size_t {
   S_CAP = 0, S_HITOFF, S_RAW, S_CHAINCNT, S_SCAN2, S_POOL_E, S_POOL_V, S_POOLCTL, S_POOLCTL1, S_FIN, S_FINCNT, S_FINROWS, S_FINOFF, S_HITS, S_ROWSPER, S_ROWOFF, S_ROWS,

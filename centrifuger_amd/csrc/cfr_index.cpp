@@ -1,5 +1,6 @@
 // cfr_index.cpp — .cfr parser (see cfr_index.hpp).  Host C++ only, no HIP.
 #include "cfr_index.hpp"
+#include "cfr_threads.hpp"
 
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -68,12 +69,7 @@ class Cursor {
       // the large arrays of a multi-Gbp index (GBs of bitvector words): slices on several threads, which also spreads the
       // page faults of the mapping (one thread reads a 15 GB file at ~4 GB/s)
       const unsigned nt = std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-      std::vector<std::thread> th;
-      for (unsigned t = 0; t < nt; ++t) th.emplace_back([=]() {
-        const size_t lo = bytes / nt * t, hi = t + 1 == nt ? bytes : bytes / nt * (t + 1);
-        memcpy((char *)dst + lo, base_ + pos_ + lo, hi - lo);
-      });
-      for (auto &x : th) x.join();
+      parallel_slices(bytes, (int)nt, [&](size_t lo, size_t hi, int) { memcpy((char *)dst + lo, base_ + pos_ + lo, hi - lo); });
     } else memcpy(dst, base_ + pos_, bytes);
     pos_ += bytes;
   }

@@ -13,6 +13,7 @@
 // 4^-d with d <= 11 and the counts are integers, so the coalesce step sums integers (weights in units of 2^-22) and is exact in
 // any order - that is what lets it run with atomics on the device.
 #include "cfr_quant.hpp"
+#include "cfr_threads.hpp"
 
 #include <zlib.h>
 
@@ -369,12 +370,7 @@ void Quant::add_tsv(const std::string &path) {
       }
       if (cur_id) { cur.id.assign(cur_id, cur_len); if (ch.groups == 1) ch.first = cur; else ch.last = cur; }
     };
-    if (nchunk == 1) parse(0);
-    else {
-      std::vector<std::thread> pool;
-      for (int c = 0; c < nchunk; ++c) pool.emplace_back(parse, c);
-      for (auto &t : pool) t.join();
-    }
+    parallel_slices((size_t)nchunk, nchunk, [&](size_t, size_t, int c) { parse(c); });   // one chunk per thread
     // stitch: the result is that of one reader walking the rows in order
     for (Chunk &ch : chunks) {
       if (ch.groups < 0) { gzclose(gz); throw FormatError{"cfr_quant: more than 65535 consecutive rows of one read id"}; }

@@ -22,7 +22,7 @@
 #include <chrono>
 #include <cstring>
 
-#include "cfr_device.hpp"
+#include "cfr_hip_util.hpp"
 #include "cfr_quant.hpp"
 
 #pragma clang fp contract(off)
@@ -31,20 +31,7 @@ namespace cfr {
 
 namespace {
 
-inline void hip_check(hipError_t e, const char *what) {
-  if (e != hipSuccess) throw HipError{std::string(what) + ": " + hipGetErrorString(e), (int)e};
-}
-#define HIP_CHECK(x) hip_check((x), #x)
-
-// the calling thread's current device is put back when a call returns: the classifier's workers drive other GPUs on the same threads
-struct DeviceScope {
-  int prev = -1;
-  explicit DeviceScope(int d) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; HIP_CHECK(hipSetDevice(d)); }
-  ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 constexpr int kBlock = 256;
-inline unsigned grid_for(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 constexpr uint32_t kSlotEmpty = 0, kEntryDead = 0xffffffffu;
 enum { CTL_ENTRIES = 0, CTL_ARENA = 1, CTL_FULL = 2, CTL_WORDS = 4 };
 
@@ -157,39 +144,47 @@ __global__ __launch_bounds__(kBlock) void k_quant_estep_sum(const uint64_t *node
   read_count[v] = acc;
 }
 
-template <class T> T *dmalloc(size_t n) {
-  void *p = nullptr;
-  HIP_CHECK(hipMalloc(&p, std::max<size_t>(n * sizeof(T), 16)));
-  return (T *)p;
-}
-template <class T> T *upload(const std::vector<T> &v, hipStream_t st) {
-  T *d = dmalloc<T>(v.size());
+template <class T> DevBuf<T> upload(const std::vector<T> &v, hipStream_t st) {
+  DevBuf<T> d(v.size());
   if (!v.empty()) HIP_CHECK(hipMemcpyAsync(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st));
   return d;
 }
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
+// the memory a QuantTable points into (all but the control block, which outlives every growth); slots and sums start cleared on st
+struct QuantTableMem {
+  uint64_t n_slots = 0, arena_cap = 0;
+  DevBuf<uint32_t> slots;
+  DevBuf<uint64_t> e_hash, e_off;
+  DevBuf<uint32_t> e_len;
+  DevBuf<unsigned long long> e_acc;
+  DevBuf<uint32_t> arena;
+  QuantTableMem() = default;
+  QuantTableMem(uint64_t n, uint64_t cap, hipStream_t st)
+      : n_slots(n), arena_cap(cap), slots(n), e_hash(n / 2), e_off(n / 2), e_len(n / 2), e_acc(3 * (n / 2)), arena(cap) {
+    HIP_CHECK(hipMemsetAsync(slots, 0, n * 4, st));
+    HIP_CHECK(hipMemsetAsync(e_acc, 0, 24 * (n / 2), st));
+  }
+  uint64_t max_entries() const { return n_slots / 2; }
+  QuantTable view(unsigned long long *ctl) const { return QuantTable{slots, n_slots, e_hash, e_off, e_len, e_acc, max_entries(), arena, arena_cap, ctl}; }
+};
+
 class DeviceCoalescer : public QuantCoalescer {
  public:
   DeviceCoalescer(int device, uint64_t table_slots) : device_(device) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) throw HipError{"cfr_quant: no HIP device " + std::to_string(device), -1};
+    if (!device_exists(device)) throw HipError{"cfr_quant: no HIP device " + std::to_string(device), -1};
     DeviceScope scope(device);
-    HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    stream_.create();
     uint64_t slots = 64;
     const uint64_t want = table_slots ? table_slots : (1ull << 21);
     while (slots < want && slots < (1ull << 31)) slots <<= 1;
-    T_.ctl = dmalloc<unsigned long long>(CTL_WORDS);
-    HIP_CHECK(hipMemsetAsync(T_.ctl, 0, CTL_WORDS * 8, stream_));
-    alloc_table(T_, slots, slots * 4);
+    ctl_.alloc(CTL_WORDS);
+    HIP_CHECK(hipMemsetAsync(ctl_, 0, CTL_WORDS * 8, stream_));
+    mem_ = QuantTableMem(slots, slots * 4, stream_);
   }
   ~DeviceCoalescer() override {
     (void)hipSetDevice(device_);
     if (stream_) (void)hipStreamSynchronize(stream_);
-    free_table(T_);
-    if (T_.ctl) (void)hipFree(T_.ctl);
-    for (Buf &b : buf_) { if (b.h_words) (void)hipHostFree(b.h_words); if (b.h_off) (void)hipHostFree(b.h_off); if (b.d_words) (void)hipFree(b.d_words); if (b.d_off) (void)hipFree(b.d_off); if (b.d_done) (void)hipFree(b.d_done); }
-    if (stream_) (void)hipStreamDestroy(stream_);
   }
   // Batches are double-buffered on the stream: batch k is copied into its pinned buffer while the device works on batch k - 1; the
   // outcome of k - 1 (did the table or the arena fill?) is looked at before k is launched.
@@ -216,16 +211,16 @@ class DeviceCoalescer : public QuantCoalescer {
     DeviceScope scope(device_);
     resolve();
     unsigned long long ctl[CTL_WORDS];
-    HIP_CHECK(hipMemcpy(ctl, T_.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
-    const uint64_t ne = ctl[CTL_ENTRIES], na = std::min<uint64_t>(ctl[CTL_ARENA], T_.arena_cap);
+    HIP_CHECK(hipMemcpy(ctl, ctl_, sizeof(ctl), hipMemcpyDeviceToHost));
+    const uint64_t ne = ctl[CTL_ENTRIES], na = std::min<uint64_t>(ctl[CTL_ARENA], mem_.arena_cap);
     std::vector<uint64_t> e_off(ne), acc(3 * ne);
     std::vector<uint32_t> e_len(ne), arena(na);
     if (ne) {
-      HIP_CHECK(hipMemcpy(e_off.data(), T_.e_off, ne * 8, hipMemcpyDeviceToHost));
-      HIP_CHECK(hipMemcpy(e_len.data(), T_.e_len, ne * 4, hipMemcpyDeviceToHost));
-      HIP_CHECK(hipMemcpy(acc.data(), T_.e_acc, ne * 24, hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(e_off.data(), mem_.e_off, ne * 8, hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(e_len.data(), mem_.e_len, ne * 4, hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(acc.data(), mem_.e_acc, ne * 24, hipMemcpyDeviceToHost));
     }
-    if (na) HIP_CHECK(hipMemcpy(arena.data(), T_.arena, na * 4, hipMemcpyDeviceToHost));
+    if (na) HIP_CHECK(hipMemcpy(arena.data(), mem_.arena, na * 4, hipMemcpyDeviceToHost));
     out = QuantAssignments();
     for (uint64_t e = 0; e < ne; ++e) {
       if (e_len[e] == kEntryDead) continue;
@@ -234,44 +229,32 @@ class DeviceCoalescer : public QuantCoalescer {
       out.begin.push_back(out.targets.size());
       out.weight_units.push_back(acc[3 * e]); out.count.push_back(acc[3 * e + 1]); out.uniq.push_back(acc[3 * e + 2]);
     }
-    stats.table_slots = T_.n_slots;
+    stats.table_slots = mem_.n_slots;
     stats.coalesce_ms += now_ms() - t0;
   }
   QuantDeviceStats stats;
 
  private:
-  struct Buf { uint32_t *h_words = nullptr, *h_off = nullptr, *d_words = nullptr, *d_off = nullptr; uint8_t *d_done = nullptr; size_t cap_words = 0, cap_n = 0; uint32_t n = 0; };
+  struct Buf { PinnedBuf<uint32_t> h_words, h_off; DevBuf<uint32_t> d_words, d_off; DevBuf<uint8_t> d_done; size_t cap_words = 0, cap_n = 0; uint32_t n = 0; };
 
-  void alloc_table(QuantTable &t, uint64_t slots, uint64_t arena_cap) {
-    t.n_slots = slots; t.max_entries = slots / 2; t.arena_cap = arena_cap;
-    t.slots = dmalloc<uint32_t>(slots);
-    t.e_hash = dmalloc<uint64_t>(t.max_entries); t.e_off = dmalloc<uint64_t>(t.max_entries); t.e_len = dmalloc<uint32_t>(t.max_entries);
-    t.e_acc = dmalloc<unsigned long long>(3 * t.max_entries);
-    t.arena = dmalloc<uint32_t>(arena_cap);
-    HIP_CHECK(hipMemsetAsync(t.slots, 0, slots * 4, stream_));
-    HIP_CHECK(hipMemsetAsync(t.e_acc, 0, 24 * t.max_entries, stream_));
-  }
-  void free_table(QuantTable &t) {
-    for (void *p : {(void *)t.slots, (void *)t.e_hash, (void *)t.e_off, (void *)t.e_len, (void *)t.e_acc, (void *)t.arena}) if (p) (void)hipFree(p);
-    t.slots = nullptr; t.e_hash = t.e_off = nullptr; t.e_len = nullptr; t.e_acc = nullptr; t.arena = nullptr;
-  }
+  // a size class grows into fresh buffers that replace the old ones only when all of them exist
   void reserve(Buf &b, size_t words, size_t n) {
     if (words > b.cap_words) {
-      if (b.h_words) { HIP_CHECK(hipHostFree(b.h_words)); HIP_CHECK(hipFree(b.d_words)); }
-      b.cap_words = std::max<size_t>(words, 1u << 16);
-      HIP_CHECK(hipHostMalloc((void **)&b.h_words, b.cap_words * 4, hipHostMallocDefault));
-      b.d_words = dmalloc<uint32_t>(b.cap_words);
+      const size_t cap = std::max<size_t>(words, 1u << 16);
+      PinnedBuf<uint32_t> h(cap);
+      DevBuf<uint32_t> d(cap);
+      b.h_words = std::move(h); b.d_words = std::move(d); b.cap_words = cap;
     }
     if (n > b.cap_n) {
-      if (b.h_off) { HIP_CHECK(hipHostFree(b.h_off)); HIP_CHECK(hipFree(b.d_off)); HIP_CHECK(hipFree(b.d_done)); }
-      b.cap_n = std::max<size_t>(n, 1u << 12);
-      HIP_CHECK(hipHostMalloc((void **)&b.h_off, (b.cap_n + 1) * 4, hipHostMallocDefault));
-      b.d_off = dmalloc<uint32_t>(b.cap_n + 1);
-      b.d_done = dmalloc<uint8_t>(b.cap_n);
+      const size_t cap = std::max<size_t>(n, 1u << 12);
+      PinnedBuf<uint32_t> h(cap + 1);
+      DevBuf<uint32_t> d(cap + 1);
+      DevBuf<uint8_t> done(cap);
+      b.h_off = std::move(h); b.d_off = std::move(d); b.d_done = std::move(done); b.cap_n = cap;
     }
   }
   void launch(const Buf &b) {
-    hipLaunchKernelGGL(k_quant_coalesce, dim3(grid_for(b.n)), dim3(kBlock), 0, stream_, T_, (const uint32_t *)b.d_words, (const uint32_t *)b.d_off, b.n, b.d_done);
+    hipLaunchKernelGGL(k_quant_coalesce, dim3(grid_for(b.n)), dim3(kBlock), 0, stream_, mem_.view(ctl_), (const uint32_t *)b.d_words, (const uint32_t *)b.d_off, b.n, b.d_done.get());
     HIP_CHECK(hipGetLastError());
   }
   // waits for the batch in flight; while it left the FULL flag: a table of twice the slots and twice the arena, the entries moved and
@@ -281,25 +264,23 @@ class DeviceCoalescer : public QuantCoalescer {
     for (;;) {
       HIP_CHECK(hipStreamSynchronize(stream_));
       unsigned long long ctl[CTL_WORDS];
-      HIP_CHECK(hipMemcpy(ctl, T_.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(ctl, ctl_, sizeof(ctl), hipMemcpyDeviceToHost));
       if (!ctl[CTL_FULL]) break;
-      if (T_.n_slots >= (1ull << 31)) throw CapacityError{"cfr_quant: more than 2^30 distinct target lists"};
-      const uint64_t ne = std::min<uint64_t>(ctl[CTL_ENTRIES], T_.max_entries), na = std::min<uint64_t>(ctl[CTL_ARENA], T_.arena_cap);
-      QuantTable N = T_;
-      alloc_table(N, T_.n_slots * 2, T_.arena_cap * 2);
+      if (mem_.n_slots >= (1ull << 31)) throw CapacityError{"cfr_quant: more than 2^30 distinct target lists"};
+      const uint64_t ne = std::min<uint64_t>(ctl[CTL_ENTRIES], mem_.max_entries()), na = std::min<uint64_t>(ctl[CTL_ARENA], mem_.arena_cap);
+      QuantTableMem N(mem_.n_slots * 2, mem_.arena_cap * 2, stream_);
       if (ne) {
-        HIP_CHECK(hipMemcpyAsync(N.e_hash, T_.e_hash, ne * 8, hipMemcpyDeviceToDevice, stream_));
-        HIP_CHECK(hipMemcpyAsync(N.e_off, T_.e_off, ne * 8, hipMemcpyDeviceToDevice, stream_));
-        HIP_CHECK(hipMemcpyAsync(N.e_len, T_.e_len, ne * 4, hipMemcpyDeviceToDevice, stream_));
-        HIP_CHECK(hipMemcpyAsync(N.e_acc, T_.e_acc, ne * 24, hipMemcpyDeviceToDevice, stream_));
+        HIP_CHECK(hipMemcpyAsync(N.e_hash, mem_.e_hash, ne * 8, hipMemcpyDeviceToDevice, stream_));
+        HIP_CHECK(hipMemcpyAsync(N.e_off, mem_.e_off, ne * 8, hipMemcpyDeviceToDevice, stream_));
+        HIP_CHECK(hipMemcpyAsync(N.e_len, mem_.e_len, ne * 4, hipMemcpyDeviceToDevice, stream_));
+        HIP_CHECK(hipMemcpyAsync(N.e_acc, mem_.e_acc, ne * 24, hipMemcpyDeviceToDevice, stream_));
       }
-      if (na) HIP_CHECK(hipMemcpyAsync(N.arena, T_.arena, na * 4, hipMemcpyDeviceToDevice, stream_));
+      if (na) HIP_CHECK(hipMemcpyAsync(N.arena, mem_.arena, na * 4, hipMemcpyDeviceToDevice, stream_));
       const unsigned long long fixed[CTL_WORDS] = {ne, na, 0, 0};
-      HIP_CHECK(hipMemcpyAsync(N.ctl, fixed, sizeof(fixed), hipMemcpyHostToDevice, stream_));
-      if (ne) { hipLaunchKernelGGL(k_quant_rehash, dim3(grid_for(ne)), dim3(kBlock), 0, stream_, N, ne); HIP_CHECK(hipGetLastError()); }
+      HIP_CHECK(hipMemcpyAsync(ctl_, fixed, sizeof(fixed), hipMemcpyHostToDevice, stream_));
+      if (ne) { hipLaunchKernelGGL(k_quant_rehash, dim3(grid_for(ne)), dim3(kBlock), 0, stream_, N.view(ctl_), ne); HIP_CHECK(hipGetLastError()); }
       HIP_CHECK(hipStreamSynchronize(stream_));
-      free_table(T_);
-      T_ = N;
+      mem_ = std::move(N);      // (the old table goes with N)
       ++stats.grow_count;
       launch(*live_);
     }
@@ -307,8 +288,9 @@ class DeviceCoalescer : public QuantCoalescer {
   }
 
   int device_;
-  hipStream_t stream_ = nullptr;
-  QuantTable T_{};
+  Stream stream_;                  // first: the last to go
+  DevBuf<unsigned long long> ctl_; // CTL_*
+  QuantTableMem mem_;
   Buf buf_[2];
   Buf *live_ = nullptr;
   size_t next_ = 0;
@@ -317,24 +299,20 @@ class DeviceCoalescer : public QuantCoalescer {
 class DeviceEStep : public QuantEStep {
  public:
   DeviceEStep(int device, const QuantCsr &c) : device_(device), n_nodes_(c.n_nodes), n_slots_(c.n_slots) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) throw HipError{"cfr_quant: no HIP device " + std::to_string(device), -1};
+    if (!device_exists(device)) throw HipError{"cfr_quant: no HIP device " + std::to_string(device), -1};
     DeviceScope scope(device);
-    HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    stream_.create();
     std::vector<uint32_t> slot_assign(c.n_slots);
     for (size_t a = 0; a + 1 < c.a_begin.size(); ++a) for (uint64_t s = c.a_begin[a]; s < c.a_begin[a + 1]; ++s) slot_assign[s] = (uint32_t)a;
     a_begin_ = upload(c.a_begin, stream_); a_target_ = upload(c.a_target, stream_); a_weight_ = upload(c.a_weight, stream_);
     slot_assign_ = upload(slot_assign, stream_); slot_pos_ = upload(c.slot_pos, stream_); node_begin_ = upload(c.node_begin, stream_);
-    terms_ = dmalloc<double>(c.n_slots); d_abund_ = dmalloc<double>(c.n_nodes); d_rc_ = dmalloc<double>(c.n_nodes);
-    HIP_CHECK(hipHostMalloc((void **)&h_pin_, std::max<size_t>(c.n_nodes, 1) * 16, hipHostMallocDefault));
+    terms_.alloc(c.n_slots); d_abund_.alloc(c.n_nodes); d_rc_.alloc(c.n_nodes);
+    h_pin_.alloc(std::max<size_t>(c.n_nodes, 1) * 2);
     HIP_CHECK(hipStreamSynchronize(stream_));   // (slot_assign is a local)
   }
   ~DeviceEStep() override {
     (void)hipSetDevice(device_);
     if (stream_) (void)hipStreamSynchronize(stream_);
-    for (void *p : {(void *)a_begin_, (void *)a_target_, (void *)a_weight_, (void *)slot_assign_, (void *)slot_pos_, (void *)node_begin_, (void *)terms_, (void *)d_abund_, (void *)d_rc_}) if (p) (void)hipFree(p);
-    if (h_pin_) (void)hipHostFree(h_pin_);
-    if (stream_) (void)hipStreamDestroy(stream_);
   }
   // one round: abund goes up and readCount comes down, each n_nodes doubles through pinned memory
   void run(const double *abund, bool init, double *read_count) override {
@@ -345,10 +323,10 @@ class DeviceEStep : public QuantEStep {
     }
     if (n_slots_) {
       hipLaunchKernelGGL(k_quant_estep_terms, dim3(grid_for(n_slots_)), dim3(kBlock), 0, stream_, (const uint64_t *)a_begin_, (const uint32_t *)a_target_,
-                         (const double *)a_weight_, (const uint32_t *)slot_assign_, (const uint64_t *)slot_pos_, (const double *)d_abund_, init ? 1 : 0, terms_, n_slots_);
+                         (const double *)a_weight_, (const uint32_t *)slot_assign_, (const uint64_t *)slot_pos_, (const double *)d_abund_, init ? 1 : 0, terms_.get(), n_slots_);
       HIP_CHECK(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_quant_estep_sum, dim3(grid_for(n_nodes_)), dim3(kBlock), 0, stream_, (const uint64_t *)node_begin_, (const double *)terms_, d_rc_, n_nodes_);
+    hipLaunchKernelGGL(k_quant_estep_sum, dim3(grid_for(n_nodes_)), dim3(kBlock), 0, stream_, (const uint64_t *)node_begin_, (const double *)terms_, d_rc_.get(), n_nodes_);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(h_pin_ + n_nodes_, d_rc_, n_nodes_ * 8, hipMemcpyDeviceToHost, stream_));
     HIP_CHECK(hipStreamSynchronize(stream_));
@@ -358,10 +336,11 @@ class DeviceEStep : public QuantEStep {
  private:
   int device_;
   uint64_t n_nodes_, n_slots_;
-  hipStream_t stream_ = nullptr;
-  uint64_t *a_begin_ = nullptr, *slot_pos_ = nullptr, *node_begin_ = nullptr;
-  uint32_t *a_target_ = nullptr, *slot_assign_ = nullptr;
-  double *a_weight_ = nullptr, *terms_ = nullptr, *d_abund_ = nullptr, *d_rc_ = nullptr, *h_pin_ = nullptr;
+  Stream stream_;                  // first: the last to go
+  DevBuf<uint64_t> a_begin_, slot_pos_, node_begin_;
+  DevBuf<uint32_t> a_target_, slot_assign_;
+  DevBuf<double> a_weight_, terms_, d_abund_, d_rc_;
+  PinnedBuf<double> h_pin_;
 };
 
 }  // namespace

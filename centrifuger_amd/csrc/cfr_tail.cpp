@@ -5,9 +5,9 @@
 // taxonomy side-table logic it calls: Taxonomy::SeqIdToTaxId / GetOrigTaxId / LCA / ReduceTaxIds
 // (Taxonomy.hpp:718-724, 633-639, 733-836, 839-973).  Pure host integer work, threaded over reads.
 #include "cfr_tail.hpp"
+#include "cfr_threads.hpp"
 
 #include <algorithm>
-#include <thread>
 
 namespace cfr {
 
@@ -244,20 +244,13 @@ void classify_batch_tail(const HostIndex &h, const DeviceIndex::BatchOut &b, siz
   if ((size_t)threads > n) threads = n ? (int)n : 1;
   std::vector<std::vector<cfr_match>> part((size_t)threads);
   std::vector<ExpandedLists> xpart(expanded ? (size_t)threads : 0);
-  auto work = [&](int tid) {
-    const size_t lo = n * (size_t)tid / (size_t)threads, hi = n * (size_t)(tid + 1) / (size_t)threads;
+  parallel_slices(n, threads, [&](size_t lo, size_t hi, int tid) {
     for (size_t i = lo; i < hi; ++i) {
       const uint64_t hb = b.hit_begin[i], he = b.hit_begin[i + 1];
       classify_read(h, b.hits.data() + hb, he - hb, b.row_begin.data() + hb, b.row_vals.data(), b.read_len[i], results[i], part[tid],
                     expanded ? &xpart[tid] : nullptr);
     }
-  };
-  if (threads == 1) work(0);
-  else {
-    std::vector<std::thread> th;
-    for (int t = 0; t < threads; ++t) th.emplace_back(work, t);
-    for (auto &x : th) x.join();
-  }
+  });
   // stitch per-thread match arrays; reads were assigned in contiguous blocks so order is preserved
   matches.clear();
   if (expanded) { expanded->spans.clear(); expanded->ids.clear(); }

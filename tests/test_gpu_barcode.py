@@ -71,6 +71,23 @@ def test_small_batches(handles, n):
     assert len(s_dev) == n and np.array_equal(s_dev, s_host) and np.array_equal(b_dev, b_host)
 
 
+def test_call_buffers_regrow_and_the_qualities_follow(tmp_path):
+    """One fresh device handle, four calls whose sizes make upload() regrow: 3 without qualities; 300 with (more than one 256-lane
+    block, both size classes regrown, the first quality buffer allocated after a regrow); 3 with; 700 without."""
+    wl = bf.random_whitelist(16, 1000)
+    path = str(tmp_path / "wl.txt")
+    bf.write_whitelist(path, wl)
+    dev, host = capi.Barcode(path, device=0), capi.Barcode(path, device=None)
+    assert dev.stats().on_device == 1
+    b, o, q, _ = bf.random_barcodes(16, 1000, N_BARCODES)
+    for n, with_qual in [(3, False), (300, True), (3, True), (700, False)]:
+        on, bn = o[:n + 1], b[:int(o[n])]
+        qn = q[:int(o[n])] if with_qual else None
+        s_dev, b_dev = dev.correct(bn, on, qn)
+        s_host, b_host = host.correct(bn, on, qn)
+        assert len(s_dev) == n and np.array_equal(s_dev, s_host) and np.array_equal(b_dev, b_host)
+
+
 def test_count_one_barcode_many_times_a_cap_and_two_calls(tmp_path):
     wl = bf.random_whitelist(16, 1000)
     path = str(tmp_path / "wl.txt")

@@ -148,8 +148,9 @@ def _rows_for_hit(h, max_entries, locate_all, min_hit_len):
     return rows
 
 
-@pytest.mark.parametrize("case", ["f6.se_default", "f6.pe_k5", "f6.se_hitk2", "f6.edge_pe_k3", "f6.long_default", "f10.se_k5"])
-def test_host_tail_from_oracle_hits_reproduces_reference_tsv(case, golden_dir):
+def _oracle_hits(case, golden_dir, n_reads=None):
+    """(index, read ids, arguments of classify_from_hits) for the first n_reads reads (all by default) of a golden case, the hits and
+    the rows' values taken from the oracle"""
     c = MAN["cases"][case]
     args = c["args"]
     kw = {}
@@ -173,6 +174,7 @@ def test_host_tail_from_oracle_hits_reproduces_reference_tsv(case, golden_dir):
     max_entries = params.max_result * params.max_result_per_hit_factor
     locate_all = params.max_result_per_hit_factor <= 0 or params.max_result <= 0
     hits, hit_begin, row_begin, row_vals, qlen = [], [0], [0], [], []
+    ids = ids[:n_reads]
     for i in range(len(ids)):
         r1 = b1[int(o1[i]):int(o1[i + 1])].tobytes()
         r2 = None if b2 is None else b2[int(o2[i]):int(o2[i + 1])].tobytes()
@@ -183,10 +185,46 @@ def test_host_tail_from_oracle_hits_reproduces_reference_tsv(case, golden_dir):
             row_begin.append(len(row_vals))
         hit_begin.append(len(hits))
         qlen.append(len(r1) + (len(r2) if r2 is not None else 0))
-    results, matches = idx.classify_from_hits(np.array(hits, dtype=capi.HIT_DTYPE), hit_begin, row_begin,
-                                              np.array(row_vals, dtype=np.uint64), qlen, threads=3)
+    return idx, ids, (np.array(hits, dtype=capi.HIT_DTYPE), hit_begin, row_begin, np.array(row_vals, dtype=np.uint64), qlen)
+
+
+@pytest.mark.parametrize("case", ["f6.se_default", "f6.pe_k5", "f6.se_hitk2", "f6.edge_pe_k3", "f6.long_default", "f10.se_k5"])
+def test_host_tail_from_oracle_hits_reproduces_reference_tsv(case, golden_dir):
+    idx, ids, args = _oracle_hits(case, golden_dir)
+    results, matches = idx.classify_from_hits(*args, threads=3)
     out = capi.tsv_header() + b"".join(idx.format_tsv(ids[i], results[i], matches) for i in range(len(ids)))
     assert out == open(os.path.join(GOLDEN, "tsv", case + ".tsv"), "rb").read()
+
+
+# ---- the slices of the host fan-out (csrc/cfr_threads.hpp), through entries that use it: every thread count gives the result of one thread
+@pytest.mark.parametrize("threads", [7, 64])
+def test_pack_reads_slices_at_the_first_threaded_length(threads):
+    """4096 * 16 + 5 bases are 4097 blocks: the shortest buffer that is packed by several threads, and its last block is ragged"""
+    rng = np.random.default_rng(21)
+    bases = rng.choice(np.frombuffer(b"ACGTNacgt\n", dtype=np.uint8), size=4096 * 16 + 5)
+    one = capi.pack_reads(bases, threads=1).copy()
+    got = capi.pack_reads(bases, threads=threads, out=np.full(4097, 0xdeadbeefdeadbeef, dtype=np.uint64))
+    assert len(one) == 4097 and np.array_equal(got, one)
+
+
+@pytest.mark.parametrize("threads", [0, 1, 8])
+@pytest.mark.parametrize("n", [0, 1, 3])
+def test_dust_slices_with_more_threads_than_reads(n, threads, golden_dir):
+    _ids, bases, offs = ora.read_fastx(os.path.join(golden_dir, "edge.fa"))
+    first = next(i for i in range(len(offs) - 3) if offs[i + 1] > offs[i])      # n reads from the first non-empty one on
+    offs = offs[first:first + n + 1]
+    one = capi.dust_mask(bases.copy(), offs, threads=1)
+    got = capi.dust_mask(bases.copy(), offs, threads=threads)
+    assert np.array_equal(got, one)
+    assert np.array_equal(got[:int(offs[0])], bases[:int(offs[0])]) and np.array_equal(got[int(offs[n]):], bases[int(offs[n]):])   # nothing outside the n reads
+
+
+def test_tail_slices_with_more_threads_than_reads(golden_dir):
+    idx, ids, args = _oracle_hits("f6.pe_k5", golden_dir, n_reads=3)
+    r1, m1 = idx.classify_from_hits(*args, threads=1)
+    r8, m8 = idx.classify_from_hits(*args, threads=8)
+    assert len(r8) == 3 and np.array_equal(r8, r1) and np.array_equal(m8, m1)
+    assert len(m1) >= 1 and int(r1["n_match"].sum()) == len(m1)
 
 
 def test_cli_rejects_out_of_scope_options_and_missing_index(golden_dir):
