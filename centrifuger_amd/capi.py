@@ -96,7 +96,7 @@ EXPORTS = [
     "cfr_merge_pairs", "cfr_merge_pairs_device", "cfr_device_index_set_merge", "cfr_classify_batch_merged",
     "cfr_classify_batch_resident_merged", "cfr_last_merge_ms",
     "cfr_quant_options_default", "cfr_quant_open", "cfr_quant_add_tsv", "cfr_quant_add_results", "cfr_quant_assignments", "cfr_quant_run",
-    "cfr_quant_values", "cfr_quant_write", "cfr_quant_get_stats", "cfr_quant_destroy",
+    "cfr_quant_values", "cfr_quant_write", "cfr_quant_get_stats", "cfr_quant_destroy", "cfr_quant_estep_probe",
     "cfr_read_format_parse", "cfr_read_format_info", "cfr_read_format_extract", "cfr_read_format_destroy",
     "cfr_barcode_open", "cfr_barcode_count", "cfr_barcode_correct", "cfr_barcode_correct_host", "cfr_barcode_counts", "cfr_barcode_get_stats",
     "cfr_barcode_destroy", "cfr_barcode_translate_open", "cfr_barcode_translate_apply", "cfr_barcode_translate_destroy",
@@ -759,6 +759,20 @@ class Quant:
             self.close()
         except Exception:
             pass
+
+
+def quant_estep_probe(a_begin, a_target, a_weight, n_nodes, abund=None, init=False, device=None):
+    """cfr_quant_estep_probe: one E-step object (device=None: the host twin) runs the init round if asked and then one round per row of
+    abund (rounds x n_nodes); returns every round's readCount, (init + rounds) x n_nodes float64"""
+    a_begin = _u64(a_begin)
+    a_target = np.ascontiguousarray(a_target, dtype=np.uint32)
+    a_weight = np.ascontiguousarray(a_weight, dtype=np.float64)
+    assert len(a_begin) == len(a_weight) + 1
+    abund = np.zeros((0, n_nodes)) if abund is None else np.ascontiguousarray(abund, dtype=np.float64).reshape(-1, n_nodes)
+    out = np.full(((1 if init else 0) + len(abund), n_nodes), -1.0, dtype=np.float64)
+    _check(lib().cfr_quant_estep_probe(C.c_int32(-1 if device is None else device), _p(a_begin), _p(a_target), _p(a_weight), C.c_size_t(len(a_weight)),
+                                       C.c_uint64(n_nodes), C.c_int32(1 if init else 0), _p(abund), C.c_size_t(len(abund)), _p(out)))
+    return out
 
 
 FORMAT_READ1, FORMAT_READ2, FORMAT_BARCODE, FORMAT_UMI = 0, 1, 2, 3

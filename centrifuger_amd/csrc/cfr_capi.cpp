@@ -639,6 +639,33 @@ void cfr_quant_destroy(cfr_quant *q) {
   delete q;
 }
 
+cfr_status cfr_quant_estep_probe(int32_t device, const uint64_t *a_begin, const uint32_t *a_target, const double *a_weight, size_t n_assign,
+                                 uint64_t n_nodes, int32_t init_round, const double *abund, size_t n_rounds, double *out_read_count) {
+  if (!a_begin || (n_assign && !a_weight) || (n_rounds && !abund) || ((init_round || n_rounds) && !out_read_count))
+    return bad_arg("cfr_quant_estep_probe: null argument");
+  if (n_nodes == 0 || n_nodes >= 0xffffffffull) return bad_arg("cfr_quant_estep_probe: n_nodes must be 1 .. 2^32 - 2");
+  if (a_begin[0] != 0) return bad_arg("cfr_quant_estep_probe: a_begin[0] must be 0");
+  for (size_t i = 0; i < n_assign; ++i)
+    if (a_begin[i + 1] < a_begin[i]) return bad_arg("cfr_quant_estep_probe: a_begin must not decrease");
+  const uint64_t n_slots = a_begin[n_assign];
+  if (n_slots && !a_target) return bad_arg("cfr_quant_estep_probe: null argument");
+  for (uint64_t s = 0; s < n_slots; ++s)
+    if (a_target[s] >= n_nodes) return bad_arg("cfr_quant_estep_probe: a target is not below n_nodes");
+  return guarded([&]() -> cfr_status {
+    cfr::QuantCsr csr;
+    csr.n_nodes = n_nodes;
+    csr.a_begin.assign(a_begin, a_begin + n_assign + 1);
+    csr.a_target.assign(a_target, a_target + n_slots);
+    csr.a_weight.assign(a_weight, a_weight + n_assign);
+    cfr::quant_csr_finish(csr);
+    std::unique_ptr<cfr::QuantEStep> estep(device >= 0 ? cfr::make_device_estep(device, csr) : cfr::make_host_estep(csr));
+    double *out = out_read_count;
+    if (init_round) { estep->run(nullptr, true, out); out += n_nodes; }
+    for (size_t k = 0; k < n_rounds; ++k, out += n_nodes) estep->run(abund + k * n_nodes, false, out);
+    return CFR_OK;
+  });
+}
+
 // ---- single-cell input: read formats, barcode whitelist, barcode translation ----
 cfr_status cfr_read_format_parse(const char *spec, cfr_read_format **out) {
   if (!spec || !out) return bad_arg("cfr_read_format_parse: null argument");

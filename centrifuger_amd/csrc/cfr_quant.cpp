@@ -199,6 +199,18 @@ struct Chunk {
 QuantCoalescer *make_host_coalescer() { return new HostCoalescer(); }
 QuantEStep *make_host_estep(const QuantCsr &c) { return new HostEStep(c); }
 
+// the node-major order of the terms: for every node its (assignment, slot) occurrences as the sequential loop meets them
+void quant_csr_finish(QuantCsr &csr) {
+  const size_t ns = csr.n_nodes;
+  csr.n_slots = csr.a_target.size();
+  csr.node_begin.assign(ns + 1, 0);
+  for (uint32_t t : csr.a_target) ++csr.node_begin[t + 1];
+  for (size_t i = 0; i < ns; ++i) csr.node_begin[i + 1] += csr.node_begin[i];
+  csr.slot_pos.resize(csr.n_slots);
+  std::vector<uint64_t> fill(csr.node_begin.begin(), csr.node_begin.end() - 1);
+  for (size_t s = 0; s < csr.n_slots; ++s) csr.slot_pos[s] = fill[csr.a_target[s]]++;
+}
+
 Quant::Quant(const std::string &prefix, const QuantOptions &o) : opt_(o) {
   load_taxonomy(prefix + ".2.cfr", tax_);
   const size_t nc = tax_.node_cnt;
@@ -481,14 +493,8 @@ int Quant::run() {
   std::vector<uint64_t> len(ns, 0);
   for (size_t i = 0; i < nc; ++i) if (to_sub[i] != 0xffffffffu) len[to_sub[i]] = taxid_length_[i] + taxid_length_[tax_.root] / 10;
 
-  // the node-major order of the terms: for every node its (assignment, slot) occurrences as the sequential loop meets them
-  csr.n_nodes = ns; csr.n_slots = csr.a_target.size();
-  csr.node_begin.assign(ns + 1, 0);
-  for (uint32_t t : csr.a_target) ++csr.node_begin[t + 1];
-  for (size_t i = 0; i < ns; ++i) csr.node_begin[i + 1] += csr.node_begin[i];
-  csr.slot_pos.resize(csr.n_slots);
-  { std::vector<uint64_t> fill(csr.node_begin.begin(), csr.node_begin.end() - 1);
-    for (size_t s = 0; s < csr.n_slots; ++s) csr.slot_pos[s] = fill[csr.a_target[s]]++; }
+  csr.n_nodes = ns;
+  quant_csr_finish(csr);
   std::unique_ptr<QuantEStep> estep(opt_.device >= 0 ? make_device_estep(opt_.device, csr) : make_host_estep(csr));
 
   // EstimateAbundanceWithEM (Quantifier.hpp:236-281)

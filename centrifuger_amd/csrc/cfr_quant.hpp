@@ -69,6 +69,8 @@ struct QuantCsr {                  // built once per quantification by the host
   std::vector<uint64_t> slot_pos;  // slot -> position of its term in the node-major order
   std::vector<uint64_t> node_begin;// node -> first position (n_nodes + 1)
 };
+// fills n_slots, node_begin and slot_pos from n_nodes, a_begin and a_target (every target < n_nodes)
+void quant_csr_finish(QuantCsr &c);
 QuantEStep *make_host_estep(const QuantCsr &c);
 
 // the device side (cfr_quant.hip); both throw HipError

@@ -402,6 +402,13 @@ cfr_status cfr_quant_values(const cfr_quant *q, const double **abund, const doub
 cfr_status cfr_quant_write(const cfr_quant *q, int format, const char *path);
 cfr_status cfr_quant_get_stats(const cfr_quant *q, cfr_quant_stats *st);
 void cfr_quant_destroy(cfr_quant *q);
+/* The E-step of EMupdate alone (Quantifier.hpp:196-208; parity probe of k_quant_estep_terms / k_quant_estep_sum and of their host
+ * twin): assignment i has the targets a_target[a_begin[i] .. a_begin[i + 1]) (each below n_nodes; a_begin[0] = 0) and the weight
+ * a_weight[i].  One E-step object is made through the seam cfr_quant_run uses (device >= 0: that GPU; -1: the host twin) and runs,
+ * in this order, the init round (weight / targetCnt) if init_round != 0 and then n_rounds rounds, round k on the n_nodes doubles at
+ * abund + k * n_nodes.  out_read_count receives every round's readCount, n_nodes doubles each: (init_round ? 1 : 0) + n_rounds vectors. */
+cfr_status cfr_quant_estep_probe(int32_t device, const uint64_t *a_begin, const uint32_t *a_target, const double *a_weight, size_t n_assign,
+                                 uint64_t n_nodes, int32_t init_round, const double *abund, size_t n_rounds, double *out_read_count);
 
 /* ---- single-cell input: read formats, barcode whitelist, barcode translation (ReadFormatter.hpp, BarcodeCorrector.hpp,
  * BarcodeTranslator.hpp; the flow of CentrifugerClass.cpp:163-224, :565-574) ----

@@ -1,6 +1,7 @@
 """centrifuger-quant on the device (k_quant_coalesce, k_quant_estep_terms / k_quant_estep_sum) against the host twin (cfr_quant with
 device = -1, itself pinned to the reference quantifier by tests/test_quant_host_cpu.py): coalesced assignments and EM values bit for
-bit, and the two command lines against the reference's reports.  -m gpu."""
+bit, and the two command lines against the reference's reports; the E-step alone (cfr_quant_estep_probe) against the sequential
+restatement of tests/quant_estep_cases.py and against the host twin, bit for bit.  -m gpu."""
 import gzip
 import os
 import subprocess
@@ -8,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import quant_estep_cases as ec
 import quant_fixtures as qf
 from centrifuger_amd import capi
 from conftest import ROOT
@@ -30,10 +32,10 @@ def _records(lists, rng=None, metas=None):
     return res, mat
 
 
-def _both(res, mat, table_slots=0):
+def _both(res, mat, table_slots=0, prefix=qf.PREFIX):
     out = []
     for device in (None, 0):
-        q = capi.Quant(qf.PREFIX, device=device, table_slots=table_slots)
+        q = capi.Quant(prefix, device=device, table_slots=table_slots)
         q.add_results(res, mat)
         out.append(qf.as_tuples(q.assignments()))
         st = q.stats()
@@ -107,10 +109,10 @@ def test_coalesce_order_prefix_and_unknown():
     assert (c[61], c[62]) in got and (c[62], c[61]) in got and (node_cnt, node_cnt) in got and (node_cnt,) in got
 
 
-def _run_both(feed):
+def _run_both(feed, prefix=qf.PREFIX):
     out = []
     for device in (None, 0):
-        q = capi.Quant(qf.PREFIX, device=device)
+        q = capi.Quant(prefix, device=device)
         feed(q)
         rounds = q.run()
         v = q.values()
@@ -178,3 +180,159 @@ def test_classifier_quant_option(key, reads, tmp_path):
         assert r.returncode == 0, r.stderr.decode()
         assert r.stdout == plain.stdout
         assert rep.read_bytes() == qf.expected(f"{key}.n{fmt}.txt"), fmt
+
+
+# ---- the wide fixture (tests/golden/quant_wide: 811 nodes, so k_quant_estep_sum runs four blocks and node indices go far beyond 13) ----
+def test_wide_em_values_equal_host_bit_for_bit():
+    host, dev = _run_both(lambda q: q.add_tsv(qf.tsv_path("wide", qf.WIDE_DIR)), prefix=qf.WIDE_PREFIX)
+    print(f"EM rounds: host {host[0]}, device {dev[0]}")
+    _assert_same_bits(host, dev)
+    assert host[0] > 100 and host[1]["abund"].any()
+
+
+def test_wide_quant_cli_device_equals_reference():
+    cases = qf.reports("wide", qf.WIDE_DIR)
+    assert len(cases) == 8
+    for name, _key, fmt, extra in cases:
+        r = qf.run_quant(["-x", qf.WIDE_PREFIX, "-c", qf.tsv_path("wide", qf.WIDE_DIR), "--output-format", str(fmt)] + extra)
+        assert r.returncode == 0, r.stderr.decode()
+        assert r.stdout == qf.expected(name, qf.WIDE_DIR), name
+        assert b"device" in r.stderr
+
+
+# ---- the E-step alone ----
+def _probe_both(case):
+    a_begin, a_target, a_weight, n_nodes, abund, init = case
+    return [capi.quant_estep_probe(a_begin, a_target, a_weight, n_nodes, abund, init=init, device=d) for d in (None, 0)]
+
+
+@pytest.mark.parametrize("n_slots", ec.GRID_SLOTS)
+@pytest.mark.parametrize("n_nodes", ec.GRID_NODES)
+def test_estep_probe_grid(n_nodes, n_slots):
+    """the edges of both grids (one lane per slot, one lane per node; blocks of 256); nodes without a term give +0.0"""
+    host, dev = _probe_both(ec.grid(n_nodes, n_slots))
+    ec.assert_same_bits(dev, ec.want("grid", n_nodes, n_slots), "device against the restatement")
+    ec.assert_same_bits(dev, host, "device against the host twin")
+    assert not ec.bits(dev[:, ec.grid_silent(n_nodes)]).any()
+
+
+@pytest.mark.parametrize("name", ["order", "long_lists", "value_range"])
+def test_estep_probe(name):
+    """order: 100 000 terms of 2^-60 .. 2^20 in one node's segment, slot order far from node-major; long_lists: a list of 5000 targets
+    over 40 nodes beside lists of 1, 2, 63, 64, 65; value_range: abund drawn by exponent down to the denormals, weights 2^-22 .. 2^40"""
+    host, dev = _probe_both(ec.get(name))
+    ec.assert_same_bits(dev, ec.want(name), "device against the restatement")
+    ec.assert_same_bits(dev, host, "device against the host twin")
+
+
+def test_estep_probe_zero_sum():
+    """one list whose targets all have abund 0: NaN at exactly its three nodes (as NaN-ness: the sign of a default NaN is the
+    platform's), equal bits everywhere else.  What each side returned there is printed."""
+    host, dev = _probe_both(ec.get("zero_sum"))
+    want = ec.want("zero_sum")
+    z = list(ec.ZERO_NODES)
+    print("NaN bits at the zero-sum nodes: device", [hex(int(x)) for x in ec.bits(dev[0, z])], "host twin", [hex(int(x)) for x in ec.bits(host[0, z])],
+          "numpy", [hex(int(x)) for x in ec.bits(want[0, z])])
+    assert np.nonzero(np.isnan(want[0]))[0].tolist() == z
+    ec.assert_same_bits(dev, want, "device against the restatement", nan_ok=True)
+    ec.assert_same_bits(host, want, "host twin against the restatement", nan_ok=True)
+
+
+def test_estep_probe_reuse():
+    """the init round and three abundance vectors through one E-step object (d_abund_, terms_ and the pinned buffer are used four
+    times): every round equals the restatement, and round 3 equals a fresh object that is given vector 3 alone"""
+    case = ec.get("reuse")
+    a_begin, a_target, a_weight, n_nodes, abund, _init = case
+    host, dev = _probe_both(case)
+    ec.assert_same_bits(dev, ec.want("reuse"), "device against the restatement")
+    ec.assert_same_bits(dev, host, "device against the host twin")
+    fresh = capi.quant_estep_probe(a_begin, a_target, a_weight, n_nodes, abund[2:3], init=False, device=0)
+    ec.assert_same_bits(dev[3:4], fresh, "round 3 of 4 against a fresh object")
+
+
+# ---- coalesce: several batches, dead entries, the arena ----
+def _records_flat(lengths, taxids, d, uniq):
+    """_records without a loop: read i has the original tax ids taxids[begin[i] .. begin[i] + lengths[i]), the weight 4^-d[i] and uniq[i]"""
+    n = len(lengths)
+    begin = np.concatenate([[0], np.cumsum(lengths)]).astype(np.uint64)
+    res = np.zeros(n, dtype=capi.RESULT_DTYPE)
+    res["score"] = 1000
+    res["secondary_score"] = np.where(uniq, 0, 1000)
+    res["hit_length"] = np.where(d > 0, 150 - 1 - d, 150)
+    res["query_length"] = 150
+    res["n_match"] = lengths
+    res["match_begin"] = begin[:-1]
+    mat = np.zeros(int(begin[-1]), dtype=capi.MATCH_DTYPE)
+    mat["taxid"] = taxids
+    return res, mat
+
+
+def _wide_ids():
+    return np.array(qf.orig_taxids(qf.WIDE_PREFIX) + [99999], dtype=np.uint64)        # 99999: not in the tree -> node_cnt
+
+
+def test_coalesce_three_batches():
+    """2^21 + 5000 records in one add_results call: the records are handed to the coalescer in batches of 2^20, 2^20 and (at finish)
+    5000, so both pinned buffers are used, the first one twice.  Batch 1 draws from 5000 lists of 2 targets, batch 2 from 5000 lists
+    of 3, batch 3 is 5000 distinct lists of 850 - more words than batch 1, so the first buffer is regrown on its second use.  Every
+    batch brings more new lists than the table has room for: a 64-slot table grows while batch 1 is resolved (inside the add of batch 2),
+    while batch 2 is resolved (inside the add of batch 3), and at finish"""
+    ids = _wide_ids()
+    rng = np.random.default_rng(21)
+    n1 = 1 << 20
+    j1, j2, j3 = rng.integers(0, 5000, size=n1), rng.integers(0, 5000, size=n1), np.arange(5000)
+    t1 = np.stack([j1 % 812, j1 // 812], axis=1)
+    t2 = np.stack([j2 % 812, j2 // 812, np.full(n1, 5)], axis=1)
+    t3 = rng.integers(0, 812, size=(5000, 850))
+    t3[:, 0], t3[:, 1] = j3 % 812, j3 // 812
+    assert 5000 * (850 + 2) > n1 * (2 + 2)
+    lengths = np.concatenate([np.full(n1, 2), np.full(n1, 3), np.full(5000, 850)])
+    taxids = ids[np.concatenate([t1.ravel(), t2.ravel(), t3.ravel()])]
+    n = len(lengths)
+    assert n == (1 << 21) + 5000
+    res, mat = _records_flat(lengths, taxids, rng.integers(0, 12, size=n), rng.integers(0, 2, size=n))
+    host, dev, st = _both(res, mat, table_slots=64, prefix=qf.WIDE_PREFIX)
+    distinct = len(host)
+    by_len = {k: sum(1 for t, _w, _c, _u in host if len(t) == k) for k in (2, 3, 850)}
+    print(f"distinct {distinct} {by_len}, grow_count {st.grow_count}, table_slots {st.table_slots}")
+    assert min(by_len.values()) >= 4097 and sum(by_len.values()) == distinct
+    assert dev == host and sum(c for _t, _w, c, _u in dev) == n
+    assert st.grow_count >= int(np.ceil(np.log2(2 * distinct / 64))) and st.table_slots >= 2 * distinct
+
+
+def test_coalesce_dead_entries_then_growth():
+    """4097 distinct lists, 40 copies of each in random order, a table of 64 slots: lanes that hold the same list write an entry each
+    and all but one lose the slot (dead entries); the growths that follow carry the dead entries along and must skip them"""
+    ids = _wide_ids()
+    rng = np.random.default_rng(40)
+    j = rng.permutation(np.repeat(np.arange(4097), 40))
+    t = np.stack([j % 812, j // 812, (7 * j) % 812], axis=1)
+    n = len(j)
+    res, mat = _records_flat(np.full(n, 3), ids[t.ravel()], rng.integers(0, 12, size=n), rng.integers(0, 2, size=n))
+    host, dev, st = _both(res, mat, table_slots=64, prefix=qf.WIDE_PREFIX)
+    print(f"grow_count {st.grow_count}, table_slots {st.table_slots}")
+    assert dev == host and len(dev) == 4097 and sum(c for _t, _w, c, _u in dev) == n
+    assert all(c == 40 for _t, _w, c, _u in dev)
+    assert st.grow_count >= 8 and st.table_slots >= 2 * 4097
+
+
+def test_coalesce_arena_fills_first():
+    """18 records, so entries (live and dead) stay below the 32 a 64-slot table holds: every growth is the arena's (256 words at the
+    start, doubled until the keys fit; the longest alone needs 65535 = 256 * 2^8).  Lists of 1, 2, 255, 256, 257, 4096 and 65535 targets;
+    each of the five long ones has a twin that differs in its last word only and a twin without the last word; the list of 2 is given twice"""
+    ids = _wide_ids()
+    rng = np.random.default_rng(65535)
+    lists = [ids[rng.integers(0, 812, size=k)].tolist() for k in (1, 2)]
+    lists.append(list(lists[1]))
+    for k in (255, 256, 257, 4096, 65535):
+        t = ids[rng.integers(0, 811, size=k)].tolist()
+        lists += [t, t[:-1] + [99999], t[:-1]]
+    assert len(lists) == 18 <= 30
+    order = rng.permutation(len(lists))
+    lists = [lists[i] for i in order]
+    host, dev, st = _both(*_records(lists, rng), table_slots=64, prefix=qf.WIDE_PREFIX)
+    print(f"grow_count {st.grow_count}, table_slots {st.table_slots}")
+    assert dev == host and len(dev) == 17 and sum(c for _t, _w, c, _u in dev) == 18
+    assert [c for t, _w, c, _u in dev if len(t) == 2] == [2] and sorted(c for t, _w, c, _u in dev if len(t) != 2) == [1] * 16
+    assert sorted(len(t) for t, _w, _c, _u in dev) == sorted([1, 2] + [k - e for k in (255, 256, 257, 4096, 65535) for e in (0, 0, 1)])
+    assert st.grow_count >= 8
