@@ -101,6 +101,9 @@ EXPORTS = [
     "cfr_barcode_open", "cfr_barcode_count", "cfr_barcode_correct", "cfr_barcode_correct_host", "cfr_barcode_counts", "cfr_barcode_get_stats",
     "cfr_barcode_destroy", "cfr_barcode_translate_open", "cfr_barcode_translate_apply", "cfr_barcode_translate_destroy",
     "cfr_tsv_header_ex", "cfr_format_tsv_ex",
+    "cfr_taxonomy_open", "cfr_taxonomy_get_tables", "cfr_taxonomy_tax_name", "cfr_taxonomy_seq_name", "cfr_tax_rank_string", "cfr_taxonomy_close",
+    "cfr_promote_open", "cfr_promote_apply", "cfr_promote_lca_warnings", "cfr_promote_get_stats", "cfr_promote_close",
+    "cfr_device_index_set_promote", "cfr_last_promote_ms",
 ]
 
 _lib = None
@@ -125,12 +128,20 @@ def lib():
             if name not in ("cfr_last_error", "cfr_version", "cfr_tsv_header", "cfr_format_tsv", "cfr_index_destroy", "cfr_format_tsv_expanded", "cfr_tsv_header_expanded",
                             "cfr_device_index_destroy", "cfr_params_default", "cfr_host_alloc", "cfr_host_free", "cfr_build_options_default",
                             "cfr_quant_options_default", "cfr_quant_destroy", "cfr_read_format_destroy", "cfr_barcode_destroy",
-                            "cfr_barcode_translate_destroy", "cfr_tsv_header_ex", "cfr_format_tsv_ex"):
+                            "cfr_barcode_translate_destroy", "cfr_tsv_header_ex", "cfr_format_tsv_ex",
+                            "cfr_taxonomy_tax_name", "cfr_taxonomy_seq_name", "cfr_tax_rank_string", "cfr_taxonomy_close"):
                 getattr(L, name).restype = C.c_int
         for name in ("cfr_quant_destroy", "cfr_read_format_destroy", "cfr_barcode_destroy", "cfr_barcode_translate_destroy"):
             getattr(L, name).restype = None
             getattr(L, name).argtypes = [C.c_void_p]
         L.cfr_tsv_header_ex.restype = C.c_char_p
+        for name in ("cfr_taxonomy_tax_name", "cfr_taxonomy_seq_name"):
+            getattr(L, name).restype = C.c_char_p
+            getattr(L, name).argtypes = [C.c_void_p, C.c_uint64]
+        L.cfr_tax_rank_string.restype = C.c_char_p
+        L.cfr_tax_rank_string.argtypes = [C.c_uint8]
+        L.cfr_taxonomy_close.restype = None
+        L.cfr_taxonomy_close.argtypes = [C.c_void_p]
         L.cfr_format_tsv_ex.restype = C.c_size_t
         _lib = L
     return _lib
@@ -412,6 +423,16 @@ class DeviceIndex:
                                                         C.c_size_t(n), C.c_uint64(total1), C.c_uint64(total2), _p(results), _p(matches),
                                                         C.c_size_t(len(matches)), C.byref(nm), _p(kind)))
         return results, matches[:nm.value], kind
+
+    def set_promote(self, level):
+        """cfr_device_index_set_promote: every following wide classify call promotes its results to `level` ("lca" or a rank string) in
+        HBM before they are copied out; None switches it off"""
+        _check(lib().cfr_device_index_set_promote(self._d, None if level is None else level.encode()))
+
+    def last_promote_ms(self) -> float:
+        ms = C.c_float(0)
+        _check(lib().cfr_last_promote_ms(self._d, C.byref(ms)))
+        return ms.value
 
     def last_merge_ms(self) -> float:
         ms = C.c_float(0)
@@ -776,6 +797,102 @@ def quant_estep_probe(a_begin, a_target, a_weight, n_nodes, abund=None, init=Fal
 
 
 FORMAT_READ1, FORMAT_READ2, FORMAT_BARCODE, FORMAT_UMI = 0, 1, 2, 3
+
+
+class TaxonomyTables(C.Structure):
+    _fields_ = [("node_cnt", C.c_uint64), ("seq_cnt", C.c_uint64), ("extra_seq_cnt", C.c_uint64), ("root", C.c_uint64),
+                ("n_seq_names", C.c_uint64), ("n_seq_lengths", C.c_uint64),
+                ("parent", C.c_void_p), ("orig_taxid", C.c_void_p), ("seq_to_tax", C.c_void_p), ("rank", C.c_void_p),
+                ("taxid_length", C.c_void_p), ("length_seq_id", C.c_void_p), ("length_value", C.c_void_p)]
+
+
+def tax_rank_string(rank: int) -> str:
+    return lib().cfr_tax_rank_string(C.c_uint8(rank)).decode()
+
+
+class Taxonomy:
+    """cfr_taxonomy: the taxonomy tables (and, with_lengths, the sequence and genome lengths) of an index prefix; never reads .1.cfr"""
+
+    def __init__(self, prefix: str, with_lengths: bool = False):
+        self._t = C.c_void_p()
+        _check(lib().cfr_taxonomy_open(prefix.encode(), C.c_int(1 if with_lengths else 0), C.byref(self._t)))
+        t = TaxonomyTables()
+        _check(lib().cfr_taxonomy_get_tables(self._t, C.byref(t)))
+        self.node_cnt, self.seq_cnt, self.extra_seq_cnt, self.root = t.node_cnt, t.seq_cnt, t.extra_seq_cnt, t.root
+
+        def arr(ptr, n, ct, dt):
+            if not ptr or n == 0:
+                return np.zeros(0, dtype=dt)
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ct)), shape=(n,)).copy()
+        self.parent = arr(t.parent, t.node_cnt, C.c_uint64, np.uint64)
+        self.orig_taxid = arr(t.orig_taxid, t.node_cnt, C.c_uint64, np.uint64)
+        self.rank = arr(t.rank, t.node_cnt, C.c_uint8, np.uint8)
+        self.seq_to_tax = arr(t.seq_to_tax, t.seq_cnt, C.c_uint64, np.uint64)
+        self.taxid_length = arr(t.taxid_length, t.node_cnt + 1, C.c_uint64, np.uint64) if with_lengths else None
+        self.length_seq_id = arr(t.length_seq_id, t.n_seq_lengths, C.c_uint64, np.uint64) if with_lengths else None
+        self.length_value = arr(t.length_value, t.n_seq_lengths, C.c_uint64, np.uint64) if with_lengths else None
+        self.seq_names = [lib().cfr_taxonomy_seq_name(self._t, C.c_uint64(i)).decode() for i in range(t.n_seq_names)]
+
+    def tax_name(self, ctid: int) -> str:
+        return lib().cfr_taxonomy_tax_name(self._t, C.c_uint64(ctid)).decode()
+
+    def close(self):
+        if self._t:
+            lib().cfr_taxonomy_close(self._t)
+            self._t = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PromoteStats(C.Structure):
+    _fields_ = [("table_ms", C.c_float), ("reads_ms", C.c_float)]
+
+
+class Promote:
+    """cfr_promote: centrifuger-promote on result arrays.  level: "lca" or a rank string.  device=None: the host twin, no GPU is touched."""
+
+    def __init__(self, prefix: str, level: str, device=0):
+        self._h = C.c_void_p()
+        _check(lib().cfr_promote_open(prefix.encode(), level.encode(), C.c_int(-1 if device is None else device), C.byref(self._h)))
+
+    def apply(self, results, matches, want_src=False):
+        """in place on RESULT_DTYPE / MATCH_DTYPE arrays; returns src_slot (the slot every kept slot came from) when asked"""
+        assert results.dtype == RESULT_DTYPE and matches.dtype == MATCH_DTYPE and results.flags.c_contiguous and matches.flags.c_contiguous
+        src = np.full(len(matches), np.uint64(0xffffffffffffffff), dtype=np.uint64) if want_src else None
+        _check(lib().cfr_promote_apply(self._h, _p(results), _p(matches), C.c_size_t(len(results)), _p(src)))
+        return src
+
+    def lca_warnings(self, results, matches):
+        """tax ids of the script's "Couldn't find parent of taxID" lines for these (unpromoted) reads"""
+        n = C.c_size_t(0)
+        st = lib().cfr_promote_lca_warnings(self._h, _p(results), _p(matches), C.c_size_t(len(results)), None, C.c_size_t(0), C.byref(n))
+        if st == CFR_OK:
+            return np.zeros(0, dtype=np.uint64)
+        if st != CFR_ERR_CAPACITY:
+            _check(st)
+        out = np.zeros(n.value, dtype=np.uint64)
+        _check(lib().cfr_promote_lca_warnings(self._h, _p(results), _p(matches), C.c_size_t(len(results)), _p(out), C.c_size_t(len(out)), C.byref(n)))
+        return out
+
+    def stats(self) -> PromoteStats:
+        st = PromoteStats()
+        _check(lib().cfr_promote_get_stats(self._h, C.byref(st)))
+        return st
+
+    def close(self):
+        if self._h:
+            lib().cfr_promote_close(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class ReadFormat:

@@ -16,6 +16,7 @@
 #include "cfr_barcode.hpp"
 #include "cfr_build.hpp"
 #include "cfr_device.hpp"
+#include "cfr_promote.hpp"
 #include "cfr_quant.hpp"
 #include "cfr_tail.hpp"
 #include "cfr_threads.hpp"
@@ -24,6 +25,13 @@ struct cfr_index { cfr::HostIndex *h; };
 struct cfr_read_format { cfr::ReadFormat f; };
 struct cfr_barcode { cfr::Barcode *b; };
 struct cfr_barcode_translate { cfr::BarcodeTranslate *t; };
+struct cfr_taxonomy {
+  cfr::Taxonomy tax;
+  std::vector<std::string> seq_names;                     // MapID order: a name stored twice keeps its first id
+  bool with_lengths = false;
+  std::vector<uint64_t> taxid_length, length_seq_id, length_value;
+};
+struct cfr_promote { cfr::Promote *p; };
 struct cfr_quant { cfr::Quant *q; std::vector<double> weight; int32_t rounds = 0; bool ran = false; };
 // One call at a time per device image: `busy` is held for the length of every entry that touches the image (try_lock:
 // CFR_ERR_BUSY for the second caller) and by the worker thread while it runs a submitted batch.
@@ -63,6 +71,14 @@ template <class F> cfr_status guarded(F &&f) {
   }
 }
 cfr_status bad_arg(const char *m) { g_err = m; return CFR_ERR_ARG; }
+
+// the cfr_promote handles that are open: a call on anything else is CFR_ERR_ARG, not a wild pointer
+std::mutex g_promote_mu;
+std::set<const cfr_promote *> g_promote_live;
+bool promote_live(const cfr_promote *h) {
+  std::lock_guard<std::mutex> lk(g_promote_mu);
+  return h && g_promote_live.count(h) != 0;
+}
 
 // entry guard: the image's buffers, streams and statistics belong to one call at a time
 struct BusyGuard {
@@ -329,6 +345,7 @@ cfr_status cfr_classify_batch_expanded(cfr_dev_index *d, const uint8_t *bases1, 
   if (!d || (n && (!bases1 || !offsets1 || !results)) || (match_cap && !spans) || (ids_cap && !ids)) return bad_arg("cfr_classify_batch_expanded: null argument");
   if ((bases2 == nullptr) != (offsets2 == nullptr)) return bad_arg("cfr_classify_batch_expanded: bases2/offsets2 must both be given");
   if (!d->d->host().params.output_expanded) return bad_arg("cfr_classify_batch_expanded: the index was opened without cfr_params.output_expanded");
+  if (d->d->promote()) return bad_arg("cfr_classify_batch_expanded: promotion is switched on (cfr_device_index_set_promote) and does not cover the expanded lists");
   CFR_ENTER(d, "cfr_classify_batch_expanded");
   return guarded([&]() -> cfr_status {
     d->d->classify_host(bases1, offsets1, bases2, offsets2, n, results, matches, match_cap, n_matches);
@@ -435,6 +452,7 @@ cfr_status cfr_classify_batch_resident_compact(cfr_dev_index *d, const void *d_b
                                                cfr_result_compact *results, cfr_match_compact *matches, size_t match_cap, size_t *n_matches) {
   if (!d || (n && (!d_bases1 || !d_offsets1 || !results || !matches))) return bad_arg("cfr_classify_batch_resident_compact: null argument");
   if ((d_bases2 == nullptr) != (d_offsets2 == nullptr)) return bad_arg("cfr_classify_batch_resident_compact: mate buffers must both be given");
+  if (d->d->promote()) return bad_arg("cfr_classify_batch_resident_compact: promotion is switched on (cfr_device_index_set_promote) and works on the wide layout: use cfr_classify_batch_resident");
   CFR_ENTER(d, "cfr_classify_batch_resident_compact");
   return guarded([&]() -> cfr_status {
     d->d->classify_device((const uint8_t *)d_bases1, (const uint64_t *)d_offsets1, (const uint8_t *)d_bases2,
@@ -664,6 +682,118 @@ cfr_status cfr_quant_estep_probe(int32_t device, const uint64_t *a_begin, const 
     for (size_t k = 0; k < n_rounds; ++k, out += n_nodes) estep->run(abund + k * n_nodes, false, out);
     return CFR_OK;
   });
+}
+
+// ---- centrifuger-inspect ----
+cfr_status cfr_taxonomy_open(const char *idx_prefix, int with_lengths, cfr_taxonomy **out) {
+  if (!idx_prefix || !out) return bad_arg("cfr_taxonomy_open: null argument");
+  *out = nullptr;
+  return guarded([&]() -> cfr_status {
+    std::unique_ptr<cfr_taxonomy> t(new cfr_taxonomy());
+    cfr::load_taxonomy(std::string(idx_prefix) + ".2.cfr", t->tax);
+    const uint64_t nc = t->tax.node_cnt;
+    if (t->tax.rank.size() < nc || t->tax.orig_taxid.size() < nc) throw cfr::FormatError{std::string(idx_prefix) + ".2.cfr: taxonomy tables shorter than the node count"};
+    for (uint64_t i = 0; i < nc; ++i)
+      if (t->tax.parent[i] >= nc) throw cfr::FormatError{std::string(idx_prefix) + ".2.cfr: the parent of node " + std::to_string(i) + " is outside the tree"};
+    std::set<std::string> seen;
+    for (const std::string &s : t->tax.seq_name) if (seen.insert(s).second) t->seq_names.push_back(s);
+    if (with_lengths) {
+      t->with_lengths = true;
+      const std::map<uint64_t, uint64_t> len = cfr::read_seq_lengths(idx_prefix);
+      for (const auto &kv : len) { t->length_seq_id.push_back(kv.first); t->length_value.push_back(kv.second); }
+      cfr::tax_genome_lengths(t->tax, len, t->taxid_length);
+    }
+    *out = t.release();
+    return CFR_OK;
+  });
+}
+
+cfr_status cfr_taxonomy_get_tables(const cfr_taxonomy *t, cfr_taxonomy_tables *o) {
+  if (!t || !o) return bad_arg("cfr_taxonomy_get_tables: null argument");
+  memset(o, 0, sizeof(*o));
+  o->node_cnt = t->tax.node_cnt; o->seq_cnt = t->tax.seq_cnt; o->extra_seq_cnt = t->tax.extra_seq_cnt; o->root = t->tax.root;
+  o->n_seq_names = t->seq_names.size(); o->n_seq_lengths = t->length_seq_id.size();
+  o->parent = t->tax.parent.data(); o->orig_taxid = t->tax.orig_taxid.data(); o->seq_to_tax = t->tax.seq_to_tax.data(); o->rank = t->tax.rank.data();
+  if (t->with_lengths) { o->taxid_length = t->taxid_length.data(); o->length_seq_id = t->length_seq_id.data(); o->length_value = t->length_value.data(); }
+  return CFR_OK;
+}
+
+const char *cfr_taxonomy_tax_name(const cfr_taxonomy *t, uint64_t ctid) {
+  if (!t || ctid >= t->tax.node_cnt) return "Unknown";
+  return t->tax.tax_name[ctid].c_str();
+}
+const char *cfr_taxonomy_seq_name(const cfr_taxonomy *t, uint64_t seq_id) {
+  if (!t || seq_id >= t->seq_names.size()) return nullptr;
+  return t->seq_names[seq_id].c_str();
+}
+const char *cfr_tax_rank_string(uint8_t rank) { return cfr::quant_rank_string(rank); }
+void cfr_taxonomy_close(cfr_taxonomy *t) { delete t; }
+
+// ---- centrifuger-promote ----
+cfr_status cfr_promote_open(const char *idx_prefix, const char *level, int device, cfr_promote **out) {
+  if (!idx_prefix || !level || !out) return bad_arg("cfr_promote_open: null argument");
+  *out = nullptr;
+  if (device < -1) return bad_arg("cfr_promote_open: device is a HIP ordinal, or -1 for the host twin");
+  return guarded([&]() -> cfr_status {
+    std::unique_ptr<cfr_promote> h(new cfr_promote{nullptr});
+    h->p = new cfr::Promote(idx_prefix, level, device);
+    { std::lock_guard<std::mutex> lk(g_promote_mu); g_promote_live.insert(h.get()); }
+    *out = h.release();
+    return CFR_OK;
+  });
+}
+
+cfr_status cfr_promote_apply(cfr_promote *h, cfr_result *results, cfr_match *matches, size_t n, uint64_t *src_slot) {
+  if (!promote_live(h)) return bad_arg("cfr_promote_apply: not an open cfr_promote handle");
+  if (n && !results) return bad_arg("cfr_promote_apply: null argument");
+  for (size_t i = 0; i < n; ++i) {
+    if (results[i].n_match > 0 && !matches) return bad_arg("cfr_promote_apply: null argument");
+    if (results[i].n_match > 0 && results[i].match_begin + (uint64_t)results[i].n_match < results[i].match_begin) return bad_arg("cfr_promote_apply: match_begin + n_match wraps");
+  }
+  return guarded([&]() -> cfr_status { h->p->apply(results, matches, n, src_slot); return CFR_OK; });
+}
+
+cfr_status cfr_promote_lca_warnings(cfr_promote *h, const cfr_result *results, const cfr_match *matches, size_t n, uint64_t *taxids, size_t cap,
+                                    size_t *count) {
+  if (!promote_live(h)) return bad_arg("cfr_promote_lca_warnings: not an open cfr_promote handle");
+  if (!count || (n && !results) || (cap && !taxids)) return bad_arg("cfr_promote_lca_warnings: null argument");
+  for (size_t i = 0; i < n; ++i) if (results[i].n_match > 0 && !matches) return bad_arg("cfr_promote_lca_warnings: null argument");
+  return guarded([&]() -> cfr_status {
+    std::vector<uint64_t> w;
+    h->p->lca_warnings(results, matches, n, w);
+    *count = w.size();
+    if (w.size() > cap) { g_err = "cfr_promote_lca_warnings: tax id buffer too small"; return CFR_ERR_CAPACITY; }
+    if (!w.empty()) memcpy(taxids, w.data(), w.size() * 8);
+    return CFR_OK;
+  });
+}
+
+cfr_status cfr_promote_get_stats(cfr_promote *h, cfr_promote_stats *st) {
+  if (!promote_live(h)) return bad_arg("cfr_promote_get_stats: not an open cfr_promote handle");
+  if (!st) return bad_arg("cfr_promote_get_stats: null argument");
+  st->table_ms = h->p->table_ms(); st->reads_ms = h->p->reads_ms();
+  return CFR_OK;
+}
+
+cfr_status cfr_promote_close(cfr_promote *h) {
+  {
+    std::lock_guard<std::mutex> lk(g_promote_mu);
+    if (!h || !g_promote_live.erase(h)) return bad_arg("cfr_promote_close: not an open cfr_promote handle");
+  }
+  delete h->p;
+  delete h;
+  return CFR_OK;
+}
+
+cfr_status cfr_device_index_set_promote(cfr_dev_index *d, const char *level) {
+  if (!d) return bad_arg("cfr_device_index_set_promote: null argument");
+  CFR_ENTER(d, "cfr_device_index_set_promote");
+  return guarded([&]() -> cfr_status { d->d->set_promote(level); return CFR_OK; });
+}
+cfr_status cfr_last_promote_ms(const cfr_dev_index *d, float *ms) {
+  if (!d || !ms) return bad_arg("cfr_last_promote_ms: null argument");
+  *ms = d->d->last_promote_ms;
+  return CFR_OK;
 }
 
 // ---- single-cell input: read formats, barcode whitelist, barcode translation ----

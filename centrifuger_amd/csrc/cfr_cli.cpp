@@ -7,7 +7,8 @@
 // cfr_classify_batch call per batch here; batches round-robin over the GPUs given by --gpu, output stays
 // in input order.  --merge-readpair (CentrifugerClass.cpp:256-335) merges the pairs on the device inside
 // cfr_classify_batch_merged (on the host when --un / --cl need the reads).  Additive options: --gpu LIST|all,
-// --gpu-batch N, --gpu-throughput.  Options of the reference that are outside this build (barcode/UMI/
+// --gpu-batch N, --gpu-throughput, --quant FILE, and --promote LEVEL (cfr_device_index_set_promote: what centrifuger-promote does
+// to the output afterwards, done in HBM before the rows are written).  Options of the reference that are outside this build (barcode/UMI/
 // read-format/sample-sheet) are rejected with a message instead of being silently ignored.
 #include <fcntl.h>
 #include <getopt.h>
@@ -67,6 +68,9 @@ const char *kUsage =
     "\t--quant FILE: also write the abundance report of centrifuger-quant for this run to FILE (equal to centrifuger-quant -x IDX -c\n"
     "\t\tthis output, when no two adjacent reads share a read id: there every read is an assignment of its own) [no report]\n"
     "\t--quant-format INT: format of that report (0:centrifuge, 1:metaphlan, 2:CAMI, 3:kraken-report) [0]\n"
+    "\t--promote STR: promote every assignment to the rank <str> (genus, species, ...), or merge a read's assignments into their lowest\n"
+    "\t\tcommon ancestor (lca), on the GPU before the rows are written (equal to centrifuger-promote IDX this-output-without-it STR when no two\n"
+    "\t\tadjacent reads share a read id); not together with --quant or --expand-taxid [no promotion]\n"
     "\t--gpu LIST: comma separated MI355X ordinals, or 'all' [0]\n"
     "\t--gpu-batch INT: reads per device batch [262144]\n"
     "\t--gpu-balanced: also derive the text-mode tables and the locate memo on the device (+0.4 s load per Gbp, faster kernels)\n"
@@ -75,7 +79,7 @@ const char *kUsage =
     "\t-h: print this usage message\n"
     "\t-v: print the version information and quit\n";
 
-enum { OPT_UN = 1000, OPT_CL, OPT_NO_DUST, OPT_MIN_HITLEN, OPT_HITK, OPT_SECONDARY, OPT_GPU, OPT_GPU_BATCH, OPT_GPU_THROUGHPUT, OPT_GPU_FASTLOAD, OPT_GPU_BALANCED, OPT_PARSE_THREADS, OPT_EXPAND_TAXID, OPT_MERGE_READPAIR, OPT_QUANT, OPT_QUANT_FORMAT, OPT_BARCODE, OPT_UMI, OPT_READ_FORMAT, OPT_BARCODE_WHITELIST, OPT_BARCODE_TRANSLATE, OPT_UNSUPPORTED };
+enum { OPT_UN = 1000, OPT_CL, OPT_NO_DUST, OPT_MIN_HITLEN, OPT_HITK, OPT_SECONDARY, OPT_GPU, OPT_GPU_BATCH, OPT_GPU_THROUGHPUT, OPT_GPU_FASTLOAD, OPT_GPU_BALANCED, OPT_PARSE_THREADS, OPT_EXPAND_TAXID, OPT_MERGE_READPAIR, OPT_QUANT, OPT_QUANT_FORMAT, OPT_PROMOTE, OPT_BARCODE, OPT_UMI, OPT_READ_FORMAT, OPT_BARCODE_WHITELIST, OPT_BARCODE_TRANSLATE, OPT_UNSUPPORTED };
 
 void print_log(const char *fmt, ...) {   // Utils::PrintLog (compactds/Utils.hpp:369-381)
   char buffer[1024];
@@ -700,6 +704,8 @@ struct Options {
   bool merge = false;                  // --merge-readpair
   std::string quant_path;              // --quant: the abundance report of this run
   int quant_format = 0;                // --quant-format
+  std::string promote;                 // --promote: the level
+  bool has_promote = false;
   std::string un_prefix, cl_prefix;
   std::vector<int> gpus{0};
   bool all_gpus = false;
@@ -769,6 +775,7 @@ int main(int argc, char *argv[]) {
       {"parse-threads", required_argument, 0, OPT_PARSE_THREADS},
       {"sample-sheet", required_argument, 0, OPT_UNSUPPORTED}, {"merge-readpair", no_argument, 0, OPT_MERGE_READPAIR},
       {"quant", required_argument, 0, OPT_QUANT}, {"quant-format", required_argument, 0, OPT_QUANT_FORMAT},
+      {"promote", required_argument, 0, OPT_PROMOTE},
       {"expand-taxid", no_argument, 0, OPT_EXPAND_TAXID}, {"read-format", required_argument, 0, OPT_READ_FORMAT},
       {"barcode", required_argument, 0, OPT_BARCODE}, {"UMI", required_argument, 0, OPT_UMI},
       {"barcode-whitelist", required_argument, 0, OPT_BARCODE_WHITELIST}, {"barcode-translate", required_argument, 0, OPT_BARCODE_TRANSLATE},
@@ -791,6 +798,7 @@ int main(int argc, char *argv[]) {
       case OPT_MERGE_READPAIR: opt.merge = true; break;                    // CentrifugerClass.cpp:445-447
       case OPT_QUANT: opt.quant_path = optarg; break;
       case OPT_QUANT_FORMAT: opt.quant_format = atoi(optarg); break;
+      case OPT_PROMOTE: opt.promote = optarg; opt.has_promote = true; break;
       case OPT_EXPAND_TAXID: opt.params.output_expanded = 1; break;       // CentrifugerClass.cpp:453-455
       case OPT_BARCODE: opt.bc_files.push_back(optarg); break;             // CentrifugerClass.cpp:457-466
       case OPT_UMI: opt.um_files.push_back(optarg); break;
@@ -840,6 +848,14 @@ int main(int argc, char *argv[]) {
     const size_t k_slots = (size_t)(opt.params.max_result > 0 ? opt.params.max_result : 4);
     const size_t by_k = std::max<size_t>(1024, (size_t)(2e9 / (40.0 * (double)k_slots)));
     if (opt.gpu_batch > by_k) opt.gpu_batch = by_k;
+  }
+  if (opt.has_promote && !opt.quant_path.empty()) {      // (the quantifier must see the assignments as the classifier made them)
+    print_log("ERROR: --promote cannot be combined with --quant: the abundance report is estimated from unpromoted assignments. Run centrifuger-quant on the unpromoted output instead.");
+    return EXIT_FAILURE;
+  }
+  if (opt.has_promote && opt.params.output_expanded) {   // (the reference's centrifuger-promote cannot process the expandedTaxIDs column either)
+    print_log("ERROR: --promote cannot be combined with --expand-taxid: promotion does not cover the expanded tax id lists.");
+    return EXIT_FAILURE;
   }
   const bool paired = !opt.m1.empty() || !opt.inter.empty();
   if (opt.merge && !paired) {          // (the reference calls ReadPairMerger::Merge with a null mate there and does not survive it, ReadPairMerger.hpp:135-141)
@@ -1419,6 +1435,7 @@ int main(int argc, char *argv[]) {
     if (st != CFR_OK) die_status("creating the device index (this build has no CPU fallback)", st);
     if (opt.dust && !host_dust) cfr_device_index_set_dust(d, 1);
     if (opt.merge && !host_merge && (st = cfr_device_index_set_merge(d, 1)) != CFR_OK) die_status("cfr_device_index_set_merge", st);
+    if (opt.has_promote && (st = cfr_device_index_set_promote(d, opt.promote.c_str())) != CFR_OK) die_status("cfr_device_index_set_promote", st);
     devs.push_back(d);
   }
   clk.add(T_DEVICE, t0);

@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "cfr_hip_util.hpp"
+#include "cfr_promote.hpp"
 #include "cfr_tail.hpp"      // dust_mask: the host twin the device SDUST falls back to
 #include "cfr_kernels.hip.inc"
 
@@ -381,20 +382,7 @@ void DeviceIndex::init(const HostIndex &h, const cfr_device_options &opt) {
   view_.tax_orig = upload(h.tax.orig_taxid);
   view_.seq_to_tax = upload(h.tax.seq_to_tax);
   view_.tax_rank = upload(h.tax.rank);
-  {
-    const auto &par = h.tax.parent;
-    std::vector<uint32_t> depth(par.size(), 0xffffffffu);
-    std::vector<uint64_t> path;
-    for (uint64_t x0 = 0; x0 < par.size(); ++x0) {
-      path.clear();
-      uint64_t x = x0;
-      while (depth[x] == 0xffffffffu && par[x] != x && par[x] < par.size() && path.size() <= par.size()) { path.push_back(x); x = par[x]; }
-      uint32_t d = depth[x] == 0xffffffffu ? 0u : depth[x];
-      if (depth[x] == 0xffffffffu) depth[x] = 0;
-      for (size_t k = path.size(); k-- > 0;) depth[path[k]] = ++d;
-    }
-    view_.tax_depth = upload(depth);
-  }
+  view_.tax_depth = upload(promote_depths(h.tax.parent));
   view_.node_cnt = h.tax.node_cnt;
   view_.seq_cnt = h.tax.seq_cnt;
   view_.tax_root = h.tax.root;
@@ -695,6 +683,7 @@ void DeviceIndex::release() {            // idempotent: also the clean-up of a c
   (void)hipDeviceSynchronize();
   for (void *p : owned_) (void)hipFree(p);
   owned_.clear();
+  promo_table_ = nullptr; promote_on_ = false; promote_tables_ = PromoteTables{};     // (the table was one of owned_)
   for (void *p : temps_) (void)hipFree(p);
   temps_.clear();
   for (auto &s : slots_) if (s.p) (void)hipFree(s.p);
@@ -703,6 +692,7 @@ void DeviceIndex::release() {            // idempotent: also the clean-up of a c
   pinned_ = nullptr; pinned_cap_ = 0;
   auto drop_event = [](hipEvent_t &e) { if (e) (void)hipEventDestroy(e); e = nullptr; };
   for (auto &set : evs_) for (auto &e : set) drop_event(e);
+  for (auto &set : promote_ev_) for (auto &e : set) drop_event(e);
   for (auto &e : tail_done_) drop_event(e);
   for (auto &e : copy_done_) drop_event(e);
   for (auto &e : h2d_done_) drop_event(e);
@@ -1227,6 +1217,25 @@ void DeviceIndex::dust_on_device(uint8_t *d_bases, const uint64_t *d_offs, size_
 #endif
 }
 
+void DeviceIndex::set_promote(const char *level) {
+  HIP_CHECK(hipSetDevice(device_));
+  if (!level) { promote_on_ = false; return; }
+  const PromoteLevel L = promote_parse_level(level);
+  if (view_.node_cnt >= 0xffffffffull) throw HipError{"promotion needs a taxonomy below 2^32 nodes", -2};
+  uint64_t one_node = view_.node_cnt;
+  for (uint64_t i = 0; i < host_->tax.node_cnt; ++i) if (host_->tax.orig_taxid[i] == 1) one_node = i;
+  promote_tables_ = PromoteTables{view_.tax_parent, view_.tax_orig, view_.seq_to_tax, view_.tax_rank, view_.tax_depth,
+                                  view_.node_cnt, view_.seq_cnt, view_.tax_root, one_node};
+  for (auto &set : promote_ev_) for (auto &e : set) if (!e) HIP_CHECK(hipEventCreate(&e));
+  if (!L.lca) {
+    if (!promo_table_) promo_table_ = dev_alloc<uint32_t>(view_.node_cnt);
+    promote_launch_table(promote_tables_, L, promo_table_, stream_);
+    HIP_CHECK(hipStreamSynchronize(stream_));
+  }
+  promote_level_ = L;
+  promote_on_ = true;
+}
+
 void DeviceIndex::dust_mask_host(uint8_t *bases, const uint64_t *offs, size_t n) {
   HIP_CHECK(hipSetDevice(device_));
   if (n == 0) return;
@@ -1583,6 +1592,13 @@ void DeviceIndex::classify_device(const uint8_t *d_b1, const uint64_t *d_o1, con
   auto copy_out = [&](size_t k, const cfr_result *d_res, const cfr_match *d_match, uint64_t extent, const void *d_flag, unsigned long long *h_flag, hipStream_t st) {
     const size_t lo = pieces[k].first, cnt = pieces[k].second;
     const int par = (int)(k & 1);
+    if (promote_on_ && !compact) {          // --promote: the sub-batch's results rewritten where they lie, in front of their copy
+      HIP_CHECK(hipEventRecord(promote_ev_[k][0], st));
+      // (beside the next sub-batch's search it is held to the post stage's few blocks per CU, like the kernels in front of it)
+      const unsigned cap = overlap_now_ && tail_blocks_per_cu_ ? (unsigned)(num_cus_ * tail_blocks_per_cu_) : 0u;
+      promote_launch_reads(promote_tables_, promote_level_, promo_table_, const_cast<cfr_result *>(d_res), const_cast<cfr_match *>(d_match), cnt, stride * lo, nullptr, st, cap);
+      HIP_CHECK(hipEventRecord(promote_ev_[k][1], st));
+    }
     if (compact) {                          // the narrow layout is made on the device; what is copied out are its arrays
       cfr_result_compact *c_res = (cfr_result_compact *)scratch(par ? S_CRES1 : S_CRES, std::max(cnt, sb) * sizeof(cfr_result_compact));
       cfr_match_compact *c_match = (cfr_match_compact *)scratch(par ? S_CMATCH1 : S_CMATCH, (stride * std::max(cnt, sb) + 1) * sizeof(cfr_match_compact));
@@ -1802,6 +1818,8 @@ void DeviceIndex::classify_device(const uint8_t *d_b1, const uint64_t *d_o1, con
       }
     }
   }
+  last_promote_ms = 0.f;
+  if (promote_on_ && !compact) for (size_t k = 0; k < nsub; ++k) { float t = 0; if (hipEventElapsedTime(&t, promote_ev_[k][0], promote_ev_[k][1]) == hipSuccess) last_promote_ms += t; }
   if (!repeated) {                          // wall time of the device work: first event of the first piece to the last of the last
     float t = 0;
     (void)hipEventElapsedTime(&t, evs_[0][0], evs_[nsub - 1][7]);

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "cfr_index.hpp"
+#include "cfr_promote_core.hpp"
 
 namespace cfr {
 
@@ -209,12 +210,23 @@ class DeviceIndex {
                         int32_t *offset);
   float last_merge_ms = 0.f;            // device time of the merge pre-step of the last *_merged call (0 when it did not run)
 
+  // --promote (centrifuger-promote inside the run, cfr_promote.hpp): when switched on, every wide classify call rewrites the results of a
+  // sub-batch in HBM - behind its tail, in front of its copy - with the kernels of cfr_promote.hip over the image's taxonomy tables.
+  // level nullptr: off (the default: nothing new is launched).  A rank level runs k_promote_table here, once.
+  void set_promote(const char *level);
+  bool promote() const { return promote_on_; }
+  float last_promote_ms = 0.f;          // device time of the promotion kernels of the last classify call (0 when switched off)
+
  private:
   struct Merged { const uint8_t *b1; const uint64_t *o1; const uint8_t *b2; const uint64_t *o2; uint64_t t1, t2;
                   const int8_t *q1, *q2; const int32_t *dec; };                  // dec: kind[n], overlap[n], offset[n] on the device
   Merged merge_on_device(const uint8_t *d_b1, const uint64_t *d_o1, const int8_t *d_q1, const uint8_t *d_b2, const uint64_t *d_o2,
                          const int8_t *d_q2, size_t n, uint64_t total1, uint64_t total2, bool want_qual);
   bool merge_ = false, merge_ready_ = false;
+  bool promote_on_ = false;
+  PromoteLevel promote_level_{};
+  PromoteTables promote_tables_{};
+  uint32_t *promo_table_ = nullptr;      // promo[node] of the level in force (owned_; made on the first rank level)
   hipEvent_t merge_ev_[2] = {};
   void init(const HostIndex &h, const cfr_device_options &opt);
   void release();
@@ -269,6 +281,7 @@ class DeviceIndex {
   static constexpr size_t kMaxSub = 16;
   hipEvent_t evs_[kMaxSub][9] = {};      // per sub-batch: 0-2 around the search, 8 and 3-7 around the stages behind it
   hipEvent_t *ev_ = nullptr;
+  hipEvent_t promote_ev_[kMaxSub][2] = {};   // around the promotion kernel of every sub-batch (made when the switch is first turned on)
   hipStream_t copy_stream_ = nullptr, h2d_stream_ = nullptr, tail_stream_ = nullptr, dust_stream_ = nullptr;
   hipStream_t search2_stream_ = nullptr, search_stream_ = nullptr;   // the second search stream; the stream launch_search enqueues on (nullptr: stream_)
   hipEvent_t prep_done_ = nullptr;

@@ -211,31 +211,31 @@ void quant_csr_finish(QuantCsr &csr) {
   for (size_t s = 0; s < csr.n_slots; ++s) csr.slot_pos[s] = fill[csr.a_target[s]]++;
 }
 
-Quant::Quant(const std::string &prefix, const QuantOptions &o) : opt_(o) {
-  load_taxonomy(prefix + ".2.cfr", tax_);
-  const size_t nc = tax_.node_cnt;
-  if (nc >= 0xffffffffull) throw FormatError{"cfr_quant: a taxonomy of 2^32 nodes or more"};
-  for (size_t i = 0; i < tax_.orig_taxid.size(); ++i) to_compact_[tax_.orig_taxid[i]] = (uint32_t)i;   // MapID::Load (MapID.hpp:83-99): a later duplicate wins
-
-  // Quantifier::Init (Quantifier.hpp:443-457): .3.cfr is pairs of size_t (seqId, length); a later pair replaces an earlier one
+// Quantifier::Init (Quantifier.hpp:443-457), CentrifugerInspect.cpp:84-90: .3.cfr is pairs of size_t (seqId, length); a later pair
+// replaces an earlier one
+std::map<uint64_t, uint64_t> read_seq_lengths(const std::string &prefix) {
   std::map<uint64_t, uint64_t> seq_length;
-  {
-    FILE *fp = fopen((prefix + ".3.cfr").c_str(), "rb");
-    if (!fp) throw IoError{"cannot open " + prefix + ".3.cfr"};
-    uint64_t tmp[2];
-    while (fread(tmp, 8, 2, fp) == 2) seq_length[tmp[0]] = tmp[1];
-    fclose(fp);
-  }
+  FILE *fp = fopen((prefix + ".3.cfr").c_str(), "rb");
+  if (!fp) throw IoError{"cannot open " + prefix + ".3.cfr"};
+  uint64_t tmp[2];
+  while (fread(tmp, 8, 2, fp) == 2) seq_length[tmp[0]] = tmp[1];
+  fclose(fp);
+  return seq_length;
+}
+
+// the genome length of every tax id: node_cnt + 1 entries (the last one, for ids the tree does not hold, stays 0)
+void tax_genome_lengths(const Taxonomy &tax, const std::map<uint64_t, uint64_t> &seq_length, std::vector<uint64_t> &taxid_length) {
+  const size_t nc = tax.node_cnt;
   // ConvertSeqLengthToTaxLength (Taxonomy.hpp:1111-1150).  The names go through MapID::Add (MapID.hpp:30-42): a name seen twice
   // keeps its first id and takes none of its own.
   std::map<std::string, size_t> name_id;
   std::vector<std::string> names;
-  for (const std::string &s : tax_.seq_name)
+  for (const std::string &s : tax.seq_name)
     if (name_id.find(s) == name_id.end()) { size_t id = name_id.size(); name_id[s] = id; names.push_back(s); }
   std::sort(names.begin(), names.end());
-  auto seq_tax = [&](size_t id) { return id < tax_.seq_cnt ? tax_.seq_to_tax[id] : (uint64_t)nc; };
+  auto seq_tax = [&](size_t id) { return id < tax.seq_cnt ? tax.seq_to_tax[id] : (uint64_t)nc; };
   auto seq_len = [&](size_t id) { auto it = seq_length.find(id); return it == seq_length.end() ? (uint64_t)0 : it->second; };
-  taxid_length_.assign(nc + 1, 0);
+  taxid_length.assign(nc + 1, 0);
   for (size_t i = 0, j; i < names.size(); i = j) {
     const size_t id = name_id[names[i]];
     uint64_t len = seq_len(id);
@@ -245,30 +245,39 @@ Quant::Quant(const std::string &prefix, const QuantOptions &o) : opt_(o) {
       if (seq_tax(next) != taxid || !quant_next_seq_same_genome(names[j - 1].c_str(), names[j].c_str())) break;
       len += seq_len(next);
     }
-    if (taxid < nc && len > taxid_length_[taxid]) taxid_length_[taxid] = len;
+    if (taxid < nc && len > taxid_length[taxid]) taxid_length[taxid] = len;
   }
   // InferAllTaxLength(taxidLength, true) (Taxonomy.hpp:1156-1213)
   {
     std::vector<uint64_t> count(nc, 0), new_len(nc, 0);
     std::vector<char> preset(nc, 0);
-    for (size_t i = 0; i < nc; ++i) if (taxid_length_[i] != 0) { preset[i] = 1; count[i] = 1; }
+    for (size_t i = 0; i < nc; ++i) if (taxid_length[i] != 0) { preset[i] = 1; count[i] = 1; }
     for (size_t i = 0; i < nc; ++i) {
       if (!preset[i]) continue;
-      if (i == tax_.parent[i] || !tax_.leaf[i]) continue;
-      size_t p = tax_.parent[i];
+      if (i == tax.parent[i] || !tax.leaf[i]) continue;
+      size_t p = tax.parent[i];
       for (size_t guard = 0; guard <= nc; ++guard) {
         ++count[p];
-        new_len[p] += taxid_length_[i];
-        if (p == tax_.parent[p]) break;
-        p = tax_.parent[p];
+        new_len[p] += taxid_length[i];
+        if (p == tax.parent[p]) break;
+        p = tax.parent[p];
       }
     }
     for (size_t i = 0; i < nc; ++i) {
       uint64_t sum = new_len[i];
-      if (preset[i]) sum += taxid_length_[i];
-      taxid_length_[i] = count[i] == 0 ? sum : sum / count[i];
+      if (preset[i]) sum += taxid_length[i];
+      taxid_length[i] = count[i] == 0 ? sum : sum / count[i];
     }
   }
+}
+
+Quant::Quant(const std::string &prefix, const QuantOptions &o) : opt_(o) {
+  load_taxonomy(prefix + ".2.cfr", tax_);
+  const size_t nc = tax_.node_cnt;
+  if (nc >= 0xffffffffull) throw FormatError{"cfr_quant: a taxonomy of 2^32 nodes or more"};
+  for (size_t i = 0; i < tax_.orig_taxid.size(); ++i) to_compact_[tax_.orig_taxid[i]] = (uint32_t)i;   // MapID::Load (MapID.hpp:83-99): a later duplicate wins
+
+  tax_genome_lengths(tax_, read_seq_lengths(prefix), taxid_length_);
   abund_.assign(nc + 1, 0); read_count_.assign(nc + 1, 0); uniq_count_.assign(nc + 1, 0);
   coalescer_.reset(opt_.device >= 0 ? make_device_coalescer(opt_.device, opt_.table_slots) : make_host_coalescer());
 }

@@ -7,6 +7,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <map>
 #include <memory>
 #include <string>
 #include <unordered_map>
@@ -18,6 +19,10 @@ namespace cfr {
 
 // the taxonomy of <prefix>.2.cfr alone (cfr_index.cpp): quantification never opens .1.cfr
 void load_taxonomy(const std::string &path, Taxonomy &t);
+// <prefix>.3.cfr (sequence id -> length) and Taxonomy::ConvertSeqLengthToTaxLength (Taxonomy.hpp:1111-1213): the genome length of
+// every tax id, node_cnt + 1 entries.  Shared by the quantifier and by centrifuger-inspect --size-table.
+std::map<uint64_t, uint64_t> read_seq_lengths(const std::string &prefix);
+void tax_genome_lengths(const Taxonomy &t, const std::map<uint64_t, uint64_t> &seq_length, std::vector<uint64_t> &taxid_length);
 
 // Flat read assignments, one record per read: n_targets | targets[n_targets] (compact tax ids, node_cnt = not in the tree) |
 // meta (bits 0..7: d of the weight 4^-d, 0..11; bit 8: score > secondScore).  off[i] = first word of record i, off[n] = words used.

@@ -410,6 +410,61 @@ void cfr_quant_destroy(cfr_quant *q);
 cfr_status cfr_quant_estep_probe(int32_t device, const uint64_t *a_begin, const uint32_t *a_target, const double *a_weight, size_t n_assign,
                                  uint64_t n_nodes, int32_t init_round, const double *abund, size_t n_rounds, double *out_read_count);
 
+/* ---- centrifuger-inspect: what an index prefix holds besides the FM index (CentrifugerInspect.cpp) ----
+ * cfr_taxonomy_open reads <prefix>.2.cfr (Taxonomy::Load) and, with_lengths != 0, <prefix>.3.cfr (sequence id -> length) - never
+ * .1.cfr - and hands out the tables bin/centrifuger-inspect prints.  The pointers belong to the handle.
+ *   parent / orig_taxid / rank: node_cnt entries (compact tax ids; GetOrigTaxId, the rank codes of Taxonomy.hpp:25-59)
+ *   seq_to_tax: seq_cnt entries; sequence names: n_seq_names of them (MapID: a name stored twice keeps its first id)
+ *   taxid_length: node_cnt + 1 genome lengths (Taxonomy::ConvertSeqLengthToTaxLength, as cfr_quant_values hands them out)
+ *   length_seq_id / length_value: the n_seq_lengths pairs of .3.cfr in ascending sequence-id order (a later pair replaced an earlier one)
+ * taxid_length, length_seq_id and length_value are NULL when the handle was opened without lengths. */
+typedef struct cfr_taxonomy cfr_taxonomy;
+typedef struct {
+  uint64_t node_cnt, seq_cnt, extra_seq_cnt, root;
+  uint64_t n_seq_names, n_seq_lengths;
+  const uint64_t *parent, *orig_taxid, *seq_to_tax;
+  const uint8_t *rank;
+  const uint64_t *taxid_length, *length_seq_id, *length_value;
+} cfr_taxonomy_tables;
+cfr_status cfr_taxonomy_open(const char *idx_prefix, int with_lengths, cfr_taxonomy **out);
+cfr_status cfr_taxonomy_get_tables(const cfr_taxonomy *t, cfr_taxonomy_tables *tables);
+const char *cfr_taxonomy_tax_name(const cfr_taxonomy *t, uint64_t compact_taxid);   /* Taxonomy::GetTaxIdName: "Unknown" beyond the tree */
+const char *cfr_taxonomy_seq_name(const cfr_taxonomy *t, uint64_t seq_id);          /* NULL beyond n_seq_names */
+const char *cfr_tax_rank_string(uint8_t rank);                                      /* Taxonomy::GetTaxRankString (Taxonomy.hpp:497-532) */
+void cfr_taxonomy_close(cfr_taxonomy *t);
+
+/* ---- centrifuger-promote: assignments rewritten to a chosen rank, or folded into their LCA (the reference's Perl script
+ * centrifuger-promote:44-149; the semantics are stated in csrc/cfr_promote_core.hpp) ----
+ * level: "lca" or a rank string ("genus", "species", "no rank" ...); a string that names no rank is legal and promotes nothing.
+ * cfr_promote_open reads <prefix>.2.cfr only.  device = -1: the host twin alone, no GPU is touched; device >= 0: the kernels of
+ *   cfr_promote.hip on that GPU (CFR_ERR_NO_DEVICE without it: no fall-back).
+ * cfr_promote_apply: in place on results / matches as the classify entries leave them (host buffers in and out): read i owns
+ *   matches[match_begin .. + n_match); the kept matches move to the front of the read's slots and n_match becomes their number.
+ *   src_slot (may be NULL; as many entries as matches): for every kept match slot, the slot of `matches` the match came from.
+ * cfr_promote_lca_warnings: the tax ids of the "Couldn't find parent of taxID ... - directly assigned to root." lines the script
+ *   prints for these reads (as they are BEFORE cfr_promote_apply) in lca mode; none in rank mode.  Host only.  *count = their
+ *   number; CFR_ERR_CAPACITY when cap is smaller (taxids may then be NULL).
+ * A handle is used by one thread at a time; a handle that is not open (never was, or was closed) is CFR_ERR_ARG. */
+typedef struct cfr_promote cfr_promote;
+typedef struct {
+  float table_ms;     /* device time of k_promote_table, which ran once when the handle was opened (0: host twin, lca) */
+  float reads_ms;     /* device time of the per-read kernel of the last cfr_promote_apply (host twin: its wall time) */
+} cfr_promote_stats;
+cfr_status cfr_promote_open(const char *idx_prefix, const char *level, int device, cfr_promote **out);
+cfr_status cfr_promote_apply(cfr_promote *h, cfr_result *results, cfr_match *matches, size_t n, uint64_t *src_slot);
+cfr_status cfr_promote_lca_warnings(cfr_promote *h, const cfr_result *results, const cfr_match *matches, size_t n,
+                                    uint64_t *taxids, size_t cap, size_t *count);
+cfr_status cfr_promote_get_stats(cfr_promote *h, cfr_promote_stats *st);
+cfr_status cfr_promote_close(cfr_promote *h);
+/* cfr_device_index_set_promote(d, level): every following call of the wide classify entries (cfr_classify_batch, _resident,
+ * _submit / _wait, _packed, _merged, _resident_merged) promotes its results in HBM - after the tail has written a sub-batch and
+ * before the sub-batch is copied out, on the same stream, with the same kernels and the taxonomy tables of the image.  level NULL
+ * switches it off (the default; nothing new is launched then).  While it is on, cfr_classify_batch_resident_compact and
+ * cfr_classify_batch_expanded return CFR_ERR_ARG (the script cannot process the expanded column either).
+ * cfr_last_promote_ms: device time of the promotion kernels of the last classify call, all sub-batches (0 when switched off). */
+cfr_status cfr_device_index_set_promote(cfr_dev_index *d, const char *level);
+cfr_status cfr_last_promote_ms(const cfr_dev_index *d, float *ms);
+
 /* ---- single-cell input: read formats, barcode whitelist, barcode translation (ReadFormatter.hpp, BarcodeCorrector.hpp,
  * BarcodeTranslator.hpp; the flow of CentrifugerClass.cpp:163-224, :565-574) ----
  * Handles of their own, independent of any cfr_dev_index; one call at a time per handle.  Barcodes, reads and comments are flat
