@@ -104,6 +104,7 @@ EXPORTS = [
     "cfr_taxonomy_open", "cfr_taxonomy_get_tables", "cfr_taxonomy_tax_name", "cfr_taxonomy_seq_name", "cfr_tax_rank_string", "cfr_taxonomy_close",
     "cfr_promote_open", "cfr_promote_apply", "cfr_promote_lca_warnings", "cfr_promote_get_stats", "cfr_promote_close",
     "cfr_device_index_set_promote", "cfr_last_promote_ms",
+    "cfr_tokenizer_open", "cfr_tokenize", "cfr_tokenizer_fetch", "cfr_tokenizer_device_reads", "cfr_tokenizer_get_stats", "cfr_tokenizer_close",
 ]
 
 _lib = None
@@ -129,7 +130,8 @@ def lib():
                             "cfr_device_index_destroy", "cfr_params_default", "cfr_host_alloc", "cfr_host_free", "cfr_build_options_default",
                             "cfr_quant_options_default", "cfr_quant_destroy", "cfr_read_format_destroy", "cfr_barcode_destroy",
                             "cfr_barcode_translate_destroy", "cfr_tsv_header_ex", "cfr_format_tsv_ex",
-                            "cfr_taxonomy_tax_name", "cfr_taxonomy_seq_name", "cfr_tax_rank_string", "cfr_taxonomy_close"):
+                            "cfr_taxonomy_tax_name", "cfr_taxonomy_seq_name", "cfr_tax_rank_string", "cfr_taxonomy_close",
+                            "cfr_tokenizer_close"):
                 getattr(L, name).restype = C.c_int
         for name in ("cfr_quant_destroy", "cfr_read_format_destroy", "cfr_barcode_destroy", "cfr_barcode_translate_destroy"):
             getattr(L, name).restype = None
@@ -143,6 +145,8 @@ def lib():
         L.cfr_taxonomy_close.restype = None
         L.cfr_taxonomy_close.argtypes = [C.c_void_p]
         L.cfr_format_tsv_ex.restype = C.c_size_t
+        L.cfr_tokenizer_close.restype = None
+        L.cfr_tokenizer_close.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -886,6 +890,71 @@ class Promote:
     def close(self):
         if self._h:
             lib().cfr_promote_close(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+READ_RECORD_DTYPE = np.dtype([("header", "<u8"), ("qual", "<u8"), ("header_len", "<u4"), ("id_len", "<u4")])
+
+
+class TokenInfo(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("consumed", C.c_uint64), ("total_bases", C.c_uint64), ("irregular_at", C.c_uint64),
+                ("fastq", C.c_int32), ("irregular", C.c_int32), ("device_ms", C.c_double)]
+
+
+class TokenStats(C.Structure):
+    _fields_ = [("copy_in_ms", C.c_double), ("kernel_ms", C.c_double)]
+
+
+class Tokenizer:
+    """cfr_tokenizer: raw FASTA/FASTQ text -> records, 64-bit offsets, flat ASCII bases.  device=None: the host twin, no GPU is touched."""
+
+    def __init__(self, device=None):
+        self._h = C.c_void_p()
+        self._last = TokenInfo()
+        _check(lib().cfr_tokenizer_open(C.c_int(-1 if device is None else device), C.byref(self._h)))
+
+    def tokenize(self, text, final=True, max_records=0) -> TokenInfo:
+        """text: bytes or a uint8 array (kept alive by the caller for ids())"""
+        a = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else _u8(text)
+        info = TokenInfo()
+        _check(lib().cfr_tokenize(self._h, _p(a), C.c_uint64(len(a)), C.c_int(int(bool(final))), C.c_uint64(max_records), C.byref(info)))
+        self._last = info
+        return info
+
+    def fetch(self):
+        """-> (records READ_RECORD_DTYPE[n], offsets uint64[n + 1], bases uint8[total_bases]) of the last tokenize()"""
+        info = self._last
+        rec = np.zeros(info.n_records, dtype=READ_RECORD_DTYPE)
+        off = np.zeros(info.n_records + 1, dtype=np.uint64)
+        bases = np.zeros(info.total_bases, dtype=np.uint8)
+        _check(lib().cfr_tokenizer_fetch(self._h, _p(rec), _p(off), _p(bases)))
+        return rec, off, bases
+
+    def stats(self) -> TokenStats:
+        st = TokenStats()
+        _check(lib().cfr_tokenizer_get_stats(self._h, C.byref(st)))
+        return st
+
+    def device_reads(self):
+        """-> (d_bases, d_offsets) as ints, for DeviceIndex.classify_resident; valid until the next tokenize() / close()"""
+        b, o = C.c_void_p(), C.c_void_p()
+        _check(lib().cfr_tokenizer_device_reads(self._h, C.byref(b), C.byref(o)))
+        return b.value or 0, o.value or 0
+
+    @staticmethod
+    def ids(text, records):
+        t = bytes(text)
+        return [t[int(r["header"]) + 1:int(r["header"]) + 1 + int(r["id_len"])].decode("latin-1") for r in records]
+
+    def close(self):
+        if self._h:
+            lib().cfr_tokenizer_close(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -20,6 +20,7 @@
 #include "cfr_quant.hpp"
 #include "cfr_tail.hpp"
 #include "cfr_threads.hpp"
+#include "cfr_tokenize_core.hpp"
 
 struct cfr_index { cfr::HostIndex *h; };
 struct cfr_read_format { cfr::ReadFormat f; };
@@ -32,6 +33,7 @@ struct cfr_taxonomy {
   std::vector<uint64_t> taxid_length, length_seq_id, length_value;
 };
 struct cfr_promote { cfr::Promote *p; };
+struct cfr_tokenizer { cfr::Tokenizer *t; };
 struct cfr_quant { cfr::Quant *q; std::vector<double> weight; int32_t rounds = 0; bool ran = false; };
 // One call at a time per device image: `busy` is held for the length of every entry that touches the image (try_lock:
 // CFR_ERR_BUSY for the second caller) and by the worker thread while it runs a submitted batch.
@@ -78,6 +80,14 @@ std::set<const cfr_promote *> g_promote_live;
 bool promote_live(const cfr_promote *h) {
   std::lock_guard<std::mutex> lk(g_promote_mu);
   return h && g_promote_live.count(h) != 0;
+}
+
+// ... and the cfr_tokenizer handles
+std::mutex g_tokenizer_mu;
+std::set<const cfr_tokenizer *> g_tokenizer_live;
+bool tokenizer_live(const cfr_tokenizer *h) {
+  std::lock_guard<std::mutex> lk(g_tokenizer_mu);
+  return h && g_tokenizer_live.count(h) != 0;
 }
 
 // entry guard: the image's buffers, streams and statistics belong to one call at a time
@@ -794,6 +804,55 @@ cfr_status cfr_last_promote_ms(const cfr_dev_index *d, float *ms) {
   if (!d || !ms) return bad_arg("cfr_last_promote_ms: null argument");
   *ms = d->d->last_promote_ms;
   return CFR_OK;
+}
+
+// ---- the tokeniser of raw FASTA/FASTQ text (cfr_tokenize_core.hpp) ----
+cfr_status cfr_tokenizer_open(int device, cfr_tokenizer **out) {
+  if (!out) return bad_arg("cfr_tokenizer_open: null argument");
+  *out = nullptr;
+  if (device < -1) return bad_arg("cfr_tokenizer_open: device is a HIP ordinal, or -1 for the host twin");
+  return guarded([&]() -> cfr_status {
+    std::unique_ptr<cfr_tokenizer> h(new cfr_tokenizer{nullptr});
+    h->t = device < 0 ? cfr::make_tokenizer_host() : cfr::make_tokenizer_device(device);
+    { std::lock_guard<std::mutex> lk(g_tokenizer_mu); g_tokenizer_live.insert(h.get()); }
+    *out = h.release();
+    return CFR_OK;
+  });
+}
+
+cfr_status cfr_tokenize(cfr_tokenizer *t, const uint8_t *text, uint64_t len, int final, uint64_t max_records, cfr_token_info *info) {
+  if (!tokenizer_live(t)) return bad_arg("cfr_tokenize: not an open cfr_tokenizer handle");
+  if (!info || (len && !text)) return bad_arg("cfr_tokenize: null argument");
+  if (len >> 32) return bad_arg("cfr_tokenize: len must be below 2^32 (offsets inside a call are 32 bits wide on the device): hand the text over in pieces");
+  if (len && text[0] != '>' && text[0] != '@') return bad_arg("cfr_tokenize: the text starts with neither '>' (FASTA) nor '@' (FASTQ)");
+  return guarded([&]() -> cfr_status { t->t->tokenize(text, len, final, max_records, info); return CFR_OK; });
+}
+
+cfr_status cfr_tokenizer_fetch(cfr_tokenizer *t, cfr_read_record *records, uint64_t *offsets, uint8_t *bases) {
+  if (!tokenizer_live(t)) return bad_arg("cfr_tokenizer_fetch: not an open cfr_tokenizer handle");
+  return guarded([&]() -> cfr_status { t->t->fetch(records, offsets, bases); return CFR_OK; });
+}
+
+cfr_status cfr_tokenizer_device_reads(cfr_tokenizer *t, const void **d_bases, const void **d_offsets) {
+  if (!tokenizer_live(t)) return bad_arg("cfr_tokenizer_device_reads: not an open cfr_tokenizer handle");
+  if (!t->t->device_reads(d_bases, d_offsets)) return bad_arg("cfr_tokenizer_device_reads: the handle is the host twin (opened with device -1)");
+  return CFR_OK;
+}
+
+cfr_status cfr_tokenizer_get_stats(cfr_tokenizer *t, cfr_token_stats *st) {
+  if (!tokenizer_live(t)) return bad_arg("cfr_tokenizer_get_stats: not an open cfr_tokenizer handle");
+  if (!st) return bad_arg("cfr_tokenizer_get_stats: null argument");
+  t->t->stats(st);
+  return CFR_OK;
+}
+
+void cfr_tokenizer_close(cfr_tokenizer *t) {
+  {
+    std::lock_guard<std::mutex> lk(g_tokenizer_mu);
+    if (!t || !g_tokenizer_live.erase(t)) return;
+  }
+  delete t->t;
+  delete t;
 }
 
 // ---- single-cell input: read formats, barcode whitelist, barcode translation ----

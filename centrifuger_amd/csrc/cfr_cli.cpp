@@ -8,7 +8,8 @@
 // in input order.  --merge-readpair (CentrifugerClass.cpp:256-335) merges the pairs on the device inside
 // cfr_classify_batch_merged (on the host when --un / --cl need the reads).  Additive options: --gpu LIST|all,
 // --gpu-batch N, --gpu-throughput, --quant FILE, and --promote LEVEL (cfr_device_index_set_promote: what centrifuger-promote does
-// to the output afterwards, done in HBM before the rows are written).  Options of the reference that are outside this build (barcode/UMI/
+// to the output afterwards, done in HBM before the rows are written), and --gpu-parse (plain files are handed to the device workers as
+// unparsed pieces; cfr_tokenize makes the flat reads in HBM and cfr_classify_batch_resident takes them from there).  Options of the reference that are outside this build (barcode/UMI/
 // read-format/sample-sheet) are rejected with a message instead of being silently ignored.
 #include <fcntl.h>
 #include <getopt.h>
@@ -76,10 +77,11 @@ const char *kUsage =
     "\t--gpu-balanced: also derive the text-mode tables and the locate memo on the device (+0.4 s load per Gbp, faster kernels)\n"
     "\t--gpu-throughput: ... and the 68 GB K-mer table (longest load, fastest kernels) [default: neither, shortest load]\n"
     "\t--parse-threads INT: threads that parse plain single-end read files in pieces [min(-t,8); 1 = sequential reader]\n"
+    "\t--gpu-parse: tokenise plain FASTA/FASTQ files (-u, -1/-2) on the GPU that classifies them; the run falls back to the host parsers, with one log line, for what that does not cover [host parsers]\n"
     "\t-h: print this usage message\n"
     "\t-v: print the version information and quit\n";
 
-enum { OPT_UN = 1000, OPT_CL, OPT_NO_DUST, OPT_MIN_HITLEN, OPT_HITK, OPT_SECONDARY, OPT_GPU, OPT_GPU_BATCH, OPT_GPU_THROUGHPUT, OPT_GPU_FASTLOAD, OPT_GPU_BALANCED, OPT_PARSE_THREADS, OPT_EXPAND_TAXID, OPT_MERGE_READPAIR, OPT_QUANT, OPT_QUANT_FORMAT, OPT_PROMOTE, OPT_BARCODE, OPT_UMI, OPT_READ_FORMAT, OPT_BARCODE_WHITELIST, OPT_BARCODE_TRANSLATE, OPT_UNSUPPORTED };
+enum { OPT_UN = 1000, OPT_CL, OPT_NO_DUST, OPT_MIN_HITLEN, OPT_HITK, OPT_SECONDARY, OPT_GPU, OPT_GPU_BATCH, OPT_GPU_THROUGHPUT, OPT_GPU_FASTLOAD, OPT_GPU_BALANCED, OPT_PARSE_THREADS, OPT_GPU_PARSE, OPT_EXPAND_TAXID, OPT_MERGE_READPAIR, OPT_QUANT, OPT_QUANT_FORMAT, OPT_PROMOTE, OPT_BARCODE, OPT_UMI, OPT_READ_FORMAT, OPT_BARCODE_WHITELIST, OPT_BARCODE_TRANSLATE, OPT_UNSUPPORTED };
 
 void print_log(const char *fmt, ...) {   // Utils::PrintLog (compactds/Utils.hpp:369-381)
   char buffer[1024];
@@ -633,9 +635,15 @@ struct Batch {
   std::vector<size_t> part_hits;       //  the strings keep their capacity across recycling); classified reads per part
   size_t n_parts = 0;
   bool done = false;
+  // --gpu-parse: the piece(s) of the mapped read file(s) this batch stands for, not parsed yet: the device worker tokenises them
+  // (cfr_tokenize) or, when they are not regular, parses them with SeqReader.  raw_want: the records the piece was cut for;
+  // raw_first: the number of its first record in its file
+  bool raw = false;
+  const char *raw1 = nullptr, *raw2 = nullptr;
+  size_t raw1_len = 0, raw2_len = 0, raw_want = 0, raw_first = 0;
   const char *id(size_t i) const { return ids.data() + id_off[i]; }
   void reset() {   // keeps every buffer's capacity: batches are recycled, so steady state allocates (and page-faults) nothing
-    n = 0; done = false;
+    n = 0; done = false; raw = false; raw1 = raw2 = nullptr; raw1_len = raw2_len = raw_want = raw_first = 0;
     ids.clear(); id_off.clear(); qual1.clear(); qual2.clear(); q1_off.clear(); q2_off.clear(); has_qual.clear(); has_qual2.clear();
     bases1.clear(); bases2.clear(); offs1.clear(); offs2.clear(); n_parts = 0;
     bc_raw.clear(); um_raw.clear(); bc_rawq.clear(); um_rawq.clear(); bc_cm.clear(); um_cm.clear(); r1_cm.clear();
@@ -713,6 +721,7 @@ struct Options {
   bool throughput_profile = false;
   int parse_threads = 0;               // 0 = automatic
   bool balanced_profile = false;
+  bool gpu_parse = false;              // --gpu-parse: cfr_tokenize on the device instead of SeqReader, where it applies
   // single-cell input (CentrifugerClass.cpp:374-381)
   std::vector<std::string> bc_files, um_files;
   std::string read_format, whitelist, translate;
@@ -754,6 +763,17 @@ struct StageClock {
 enum { T_OPEN = 0, T_DEVICE, T_PARSE, T_DUST, T_CLASSIFY, T_FORMAT, T_WRITE, T_WALL };
 inline std::chrono::steady_clock::time_point tick() { return std::chrono::steady_clock::now(); }
 
+// .4.cfr says sequence_type amino_acid (Classifier::IsProteinDatabase); asked before the index itself is loaded
+bool index_is_protein(const std::string &prefix) {
+  bool protein = false;
+  if (FILE *f4 = fopen((prefix + ".4.cfr").c_str(), "r")) {
+    char key[128], val[128];
+    while (fscanf(f4, "%127s %127s", key, val) == 2) if (!strcmp(key, "sequence_type") && !strcmp(val, "amino_acid")) protein = true;
+    fclose(f4);
+  }
+  return protein;
+}
+
 [[noreturn]] void die_status(const char *what, cfr_status st) {
   print_log("ERROR: %s failed (status %d): %s", what, st, cfr_last_error());
   exit(EXIT_FAILURE);
@@ -772,7 +792,7 @@ int main(int argc, char *argv[]) {
       {"consider-secondary", required_argument, 0, OPT_SECONDARY}, {"gpu", required_argument, 0, OPT_GPU},
       {"gpu-batch", required_argument, 0, OPT_GPU_BATCH}, {"gpu-throughput", no_argument, 0, OPT_GPU_THROUGHPUT},
       {"gpu-fast-load", no_argument, 0, OPT_GPU_FASTLOAD}, {"gpu-balanced", no_argument, 0, OPT_GPU_BALANCED},
-      {"parse-threads", required_argument, 0, OPT_PARSE_THREADS},
+      {"parse-threads", required_argument, 0, OPT_PARSE_THREADS}, {"gpu-parse", no_argument, 0, OPT_GPU_PARSE},
       {"sample-sheet", required_argument, 0, OPT_UNSUPPORTED}, {"merge-readpair", no_argument, 0, OPT_MERGE_READPAIR},
       {"quant", required_argument, 0, OPT_QUANT}, {"quant-format", required_argument, 0, OPT_QUANT_FORMAT},
       {"promote", required_argument, 0, OPT_PROMOTE},
@@ -829,6 +849,7 @@ int main(int argc, char *argv[]) {
       case OPT_GPU_FASTLOAD: break;                      // the default; accepted for symmetry
       case OPT_GPU_BALANCED: opt.balanced_profile = true; break;
       case OPT_PARSE_THREADS: opt.parse_threads = atoi(optarg); break;
+      case OPT_GPU_PARSE: opt.gpu_parse = true; break;
       case OPT_UNSUPPORTED:
         print_log("ERROR: option --%s belongs to a part of Centrifuger outside the MI355X classification path and is not available in this build.",
                   long_options[option_index].name);
@@ -1005,6 +1026,22 @@ int main(int argc, char *argv[]) {
     for (int g = 0; g < cnt; ++g) opt.gpus.push_back(g);
     if (opt.gpus.empty()) { print_log("ERROR: no MI355X device found (this build has no CPU fallback)."); return EXIT_FAILURE; }
   }
+
+  // ---- --gpu-parse: where it applies the reader hands out unparsed pieces of the mapped files and the device workers tokenise them;
+  // everywhere else the run is what it is without the switch, and one log line says why
+  bool gpu_parse = opt.gpu_parse;
+  if (gpu_parse) {
+    const char *why = nullptr;
+    if (!opt.un_prefix.empty() || !opt.cl_prefix.empty()) why = "--un / --cl need the reads and their qualities on the host";
+    else if (opt.merge) why = "--merge-readpair needs the qualities";
+    else if (opt.params.output_expanded) why = "--expand-taxid has a classify entry of its own";
+    else if (!opt.inter.empty()) why = "interleaved files (-i) are not covered";
+    else if (single_cell) why = "the single-cell options read several files in step";
+    else if (index_is_protein(opt.idx)) why = "a protein index is not covered";
+    if (why) { print_log("--gpu-parse is not used, the reads are parsed on the host: %s.", why); gpu_parse = false; }
+  }
+  std::vector<std::unique_ptr<MappedFile>> raw_files;   // (mapped until the end of the run: batches point into them)
+  std::atomic<bool> raw_broken{false};                 // a piece came back irregular: it and every later one go through SeqReader
 
   // ---- pipeline: reader -> dust -> device workers (one per GPU) -> TSV formatter -> ordered writer (this thread)
   std::mutex mu;
@@ -1264,8 +1301,50 @@ int main(int argc, char *argv[]) {
       for (auto &x : th) x.join();
       seq_no += nchunks;
     };
+    // --gpu-parse: every file must be a plain file that the record cutter accepts (pieces of --gpu-batch records that start and end at
+    // verified record starts); otherwise nothing of the run takes this path
+    bool raw_done = false;
+    if (gpu_parse) {
+      struct RawPlan { const MappedFile *f1, *f2; std::vector<size_t> c1, c2; size_t total; };
+      std::vector<RawPlan> plans;
+      const char *why = nullptr;
+      const int pt = opt.parse_threads > 0 ? opt.parse_threads : std::min(opt.threads, 8);
+      const std::vector<std::string> &first = paired ? opt.m1 : opt.u;
+      for (size_t i = 0; i < first.size() && !why; ++i) {
+        RawPlan p{nullptr, nullptr, {}, {}, 0};
+        size_t t2 = 0;
+        auto plan = [&](const std::string &f, const MappedFile *&mf, std::vector<size_t> &cuts, size_t &total) {
+          raw_files.emplace_back(new MappedFile());
+          mf = raw_files.back().get();
+          if (f == "-" || !raw_files.back()->open_plain(f)) { why = "an input is not a plain FASTA/FASTQ file (gz, stdin, or too short)"; return; }
+          if (!plan_record_cuts(*mf, opt.gpu_batch, pt, cuts, total)) { why = "a file is not made of regular records (4-line FASTQ, or FASTA)"; return; }
+          for (size_t k = 0; k + 1 < cuts.size(); ++k) if ((cuts[k + 1] - cuts[k]) >> 32) why = "a piece of --gpu-batch records has 4 GB or more";
+        };
+        plan(first[i], p.f1, p.c1, p.total);
+        if (!why && paired) {
+          plan(opt.m2[i], p.f2, p.c2, t2);
+          if (!why && (t2 != p.total || p.c2.size() != p.c1.size())) why = "the mate files have different numbers of records";
+        }
+        plans.push_back(std::move(p));
+      }
+      if (why) print_log("--gpu-parse is not used, the reads are parsed on the host: %s.", why);
+      else {
+        for (const RawPlan &p : plans)
+          for (size_t k = 0; k + 1 < p.c1.size(); ++k) {
+            std::shared_ptr<Batch> b = fresh_batch();
+            b->seq_no = seq_no++;
+            b->raw = true;
+            b->raw_first = k * opt.gpu_batch;
+            b->raw_want = std::min(opt.gpu_batch, p.total - b->raw_first);
+            b->raw1 = p.f1->base + p.c1[k]; b->raw1_len = p.c1[k + 1] - p.c1[k];
+            if (p.f2) { b->raw2 = p.f2->base + p.c2[k]; b->raw2_len = p.c2[k + 1] - p.c2[k]; }
+            publish(b);
+          }
+        raw_done = true;
+      }
+    }
     bool pairs_done = false;
-    if (paired && opt.parse_threads != 1 && (interleaved ? opt.inter.size() == 1 : (opt.m1.size() == 1 && opt.m2.size() == 1))) {
+    if (!raw_done && paired && opt.parse_threads != 1 && (interleaved ? opt.inter.size() == 1 : (opt.m1.size() == 1 && opt.m2.size() == 1))) {
       MappedFile f1, f2;
       std::vector<size_t> c1, c2;
       size_t t1 = 0, t2 = 0;
@@ -1282,7 +1361,7 @@ int main(int argc, char *argv[]) {
         pairs_done = true;
       }
     }
-    if (pairs_done) {
+    if (pairs_done || raw_done) {
     } else
     if (!paired && opt.parse_threads != 1) {
       for (const std::string &f : opt.u) {
@@ -1322,12 +1401,7 @@ int main(int argc, char *argv[]) {
   // when the masked reads are needed on the host as well (--un / --cl write them).
   // a protein index (.4.cfr says sequence_type amino_acid, Classifier::IsProteinDatabase) is searched translated and never
   // dust-masked (CentrifugerClass.cpp:248, 276); the stage below must know before the index itself is loaded
-  bool protein = false;
-  if (FILE *f4 = fopen((opt.idx + ".4.cfr").c_str(), "r")) {
-    char key[128], val[128];
-    while (fscanf(f4, "%127s %127s", key, val) == 2) if (!strcmp(key, "sequence_type") && !strcmp(val, "amino_acid")) protein = true;
-    fclose(f4);
-  }
+  const bool protein = index_is_protein(opt.idx);
   if (protein) opt.dust = false;
   if (protein && opt.merge) {
     print_log("ERROR: --merge-readpair is not available with a protein index in this build: a merged pair is searched as one read with an "
@@ -1490,7 +1564,53 @@ int main(int argc, char *argv[]) {
   }
 
   // device stage: one thread per GPU takes dust-masked batches
+  // --gpu-parse: a raw batch on the worker's own tokeniser(s).  true: the reads are in HBM (ids in b.ids); false: the piece is not
+  // regular, nothing was taken from it
+  auto tokenize_raw = [&](Batch &b, cfr_tokenizer *tok1, cfr_tokenizer *tok2, cfr_token_info &i1, cfr_token_info &i2, std::vector<cfr_read_record> &recs) -> bool {
+    cfr_status s = cfr_tokenize(tok1, (const uint8_t *)b.raw1, b.raw1_len, 1, b.raw_want, &i1);
+    if (s != CFR_OK) die_status("cfr_tokenize", s);
+    bool ok = !i1.irregular && i1.n_records == b.raw_want && i1.consumed == b.raw1_len;
+    if (ok && b.raw2) {
+      if ((s = cfr_tokenize(tok2, (const uint8_t *)b.raw2, b.raw2_len, 1, b.raw_want, &i2)) != CFR_OK) die_status("cfr_tokenize", s);
+      ok = !i2.irregular && i2.n_records == b.raw_want && i2.consumed == b.raw2_len;
+    }
+    if (!ok) return false;
+    recs.resize(b.raw_want);
+    if ((s = cfr_tokenizer_fetch(tok1, recs.data(), nullptr, nullptr)) != CFR_OK) die_status("cfr_tokenizer_fetch", s);
+    for (size_t i = 0; i < b.raw_want; ++i) {      // the ids for the TSV: from the record table and the mapped text
+      const char *id = b.raw1 + recs[i].header + 1;
+      b.id_off.push_back(b.ids.size());
+      b.ids.insert(b.ids.end(), id, id + recs[i].id_len);
+      b.ids.push_back('\0');
+    }
+    b.n = b.raw_want;
+    return true;
+  };
+  // ... and the same pieces through SeqReader, as the parallel readers of the host path take them
+  auto parse_raw_on_host = [&](Batch &b) {
+    SeqReader rd1(b.raw1, b.raw1_len);
+    std::unique_ptr<SeqReader> rd2;
+    if (b.raw2) rd2.reset(new SeqReader(b.raw2, b.raw2_len));
+    bool hq = false, hq2 = false;
+    while (rd1.next_start() < b.raw1_len) {
+      const size_t id_at = b.ids.size();
+      if (!rd1.next_mem(&b.ids, b.bases1, nullptr, hq)) break;
+      if (rd2) {
+        if (!rd2->next_mem(nullptr, b.bases2, nullptr, hq2)) { print_log("ERROR: The two mate-pair read files have different number of reads."); exit(EXIT_FAILURE); }
+        b.offs2.push_back(b.bases2.size());
+      }
+      b.id_off.push_back(id_at);
+      b.offs1.push_back(b.bases1.size());
+      ++b.n;
+    }
+    if (rd2 && (b.n != b.raw_want || rd2->next_start() < b.raw2_len)) {
+      print_log("ERROR: the mate files are not made of regular records around pair %lu; rerun without --gpu-parse and with --parse-threads 1.", (unsigned long)(b.raw_first + b.n));
+      exit(EXIT_FAILURE);
+    }
+  };
   auto worker = [&](cfr_dev_index *dev, size_t dev_no) {
+    cfr_tokenizer *tok1 = nullptr, *tok2 = nullptr;       // --gpu-parse: opened with the first raw batch, on this worker's GPU
+    std::vector<cfr_read_record> recs;
     for (;;) {
       std::shared_ptr<Batch> b;
       {
@@ -1500,7 +1620,21 @@ int main(int argc, char *argv[]) {
         b = dusted.front();
         dusted.pop_front();
       }
-      const auto ts = tick();
+      auto ts = tick();
+      bool resident = false;
+      cfr_token_info tk1, tk2;
+      if (b->raw) {
+        if (!raw_broken.load()) {
+          for (cfr_tokenizer **t : {&tok1, &tok2})
+            if (!*t && (t == &tok1 || b->raw2)) { const cfr_status s = cfr_tokenizer_open(opt.gpus[dev_no], t); if (s != CFR_OK) die_status("cfr_tokenizer_open", s); }
+          resident = tokenize_raw(*b, tok1, tok2, tk1, tk2, recs);
+          if (!resident && !raw_broken.exchange(true))
+            print_log("--gpu-parse stops here, the rest is parsed on the host: a piece of the input is not made of regular records.");
+        }
+        if (!resident) parse_raw_on_host(*b);
+        clk.add(T_PARSE, ts);
+        ts = tick();
+      }
       if (has_barcode && b->n) {        // Correct, Translate or "N" (CentrifugerClass.cpp:186-206), on the GPU that classifies the batch
         std::vector<int8_t> status(b->n, 0);
         std::vector<uint8_t> fixed;
@@ -1555,6 +1689,11 @@ int main(int argc, char *argv[]) {
           b->exp_ids.resize(ids_cap);
           s = cfr_classify_batch_expanded(dev, in1, in_o1, in2, in_o2, b->n, b->results.data(), b->matches.data(), b->spans.data(), cap, &used,
                                           b->exp_ids.data(), ids_cap, &ids_used);
+        } else if (resident) {
+          const void *d_b1 = nullptr, *d_o1 = nullptr, *d_b2 = nullptr, *d_o2 = nullptr;
+          cfr_tokenizer_device_reads(tok1, &d_b1, &d_o1);
+          if (b->raw2) cfr_tokenizer_device_reads(tok2, &d_b2, &d_o2);
+          s = cfr_classify_batch_resident(dev, d_b1, d_o1, d_b2, d_o2, b->n, tk1.total_bases, b->raw2 ? tk2.total_bases : 0, b->results.data(), b->matches.data(), cap, &used);
         } else if (device_merge)
           s = cfr_classify_batch_merged(dev, in1, in_o1, mq1, in2, in_o2, mq2, b->n, b->results.data(), b->matches.data(), cap, &used, nullptr);
         else
@@ -1573,6 +1712,8 @@ int main(int argc, char *argv[]) {
       classified_q.push_back(b);
       cv.notify_all();
     }
+    cfr_tokenizer_close(tok1);
+    cfr_tokenizer_close(tok2);
     std::lock_guard<std::mutex> lk(mu);
     ++workers_finished;
     cv.notify_all();

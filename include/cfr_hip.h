@@ -465,6 +465,45 @@ cfr_status cfr_promote_close(cfr_promote *h);
 cfr_status cfr_device_index_set_promote(cfr_dev_index *d, const char *level);
 cfr_status cfr_last_promote_ms(const cfr_dev_index *d, float *ms);
 
+/* ---- raw FASTA/FASTQ text -> flat bases + offsets (what ReadFiles.hpp:212-330 and kseq do line by line) ----
+ * The tokeniser accepts "regular" text - 4-line FASTQ, FASTA whose sequence lines start with neither '@' nor '+' - and refuses the
+ * rest rather than guessing; the grammar is stated in csrc/cfr_tokenize_core.hpp.  What it delivers is a prefix of what the
+ * sequential grammar (kseq) reads from the same text; at the first record that breaks a rule it stops, says so (irregular,
+ * irregular_at) and the caller continues there with a sequential reader.
+ * The handle is its own, independent of any cfr_dev_index; one call at a time per handle.
+ * cfr_tokenizer_open: device = -1: the host twin, no GPU is touched; device >= 0: the kernels of cfr_tokenize.hip on that GPU
+ *   (CFR_ERR_NO_DEVICE without it: no fall-back).
+ * cfr_tokenize: text[0] must be '>' or '@' and len below 2^32 (CFR_ERR_ARG otherwise; len = 0 is CFR_OK with nothing delivered).
+ *   final != 0: the text ends here, so a last line without '\n' counts and the last FASTA record is complete.  max_records 0: no cap;
+ *   otherwise n_records = min(cap, complete records, records before the irregular one).  consumed: the offset of the header line of
+ *   the first record that was not delivered, or len.  n_records == 0 with consumed == 0 is CFR_OK: hand over more text.
+ *   The call returns with its stream synchronised.
+ * cfr_tokenizer_fetch: the result of the last cfr_tokenize to host memory; any pointer may be NULL; n_records records,
+ *   n_records + 1 offsets, total_bases bases (ASCII, bytes as they are in the text).  The id of record r is the id_len bytes at
+ *   text + header + 1.
+ * cfr_tokenizer_device_reads: device handle only (CFR_ERR_ARG on the host twin): the flat bases and the 64-bit offsets in HBM, in
+ *   the form cfr_classify_batch_resident takes; valid until the next cfr_tokenize or close on the handle.
+ * cfr_tokenizer_get_stats: the parts of the last call's device_ms. */
+typedef struct cfr_tokenizer cfr_tokenizer;
+typedef struct { uint64_t header, qual; uint32_t header_len, id_len; } cfr_read_record;   /* 24 bytes; offsets into the text; qual = 0 for FASTA */
+typedef struct {
+  uint64_t n_records, consumed, total_bases;
+  uint64_t irregular_at;      /* offset of the irregular record's header line; meaningful when irregular != 0 */
+  int32_t fastq, irregular;
+  double device_ms;           /* stream time of the last call: copy in, kernels, copies out (host twin: wall time) */
+} cfr_token_info;
+cfr_status cfr_tokenizer_open(int device, cfr_tokenizer **out);
+cfr_status cfr_tokenize(cfr_tokenizer *t, const uint8_t *text, uint64_t len, int final, uint64_t max_records, cfr_token_info *info);
+cfr_status cfr_tokenizer_fetch(cfr_tokenizer *t, cfr_read_record *records, uint64_t *offsets, uint8_t *bases);
+cfr_status cfr_tokenizer_device_reads(cfr_tokenizer *t, const void **d_bases, const void **d_offsets);
+/* the parts of device_ms of the last cfr_tokenize, from events on the handle's stream (both 0 on the host twin) */
+typedef struct {
+  double copy_in_ms;          /* the text to the device, its padding */
+  double kernel_ms;           /* the five kernels and the scans, the wait for the line count between them included */
+} cfr_token_stats;
+cfr_status cfr_tokenizer_get_stats(cfr_tokenizer *t, cfr_token_stats *st);
+void cfr_tokenizer_close(cfr_tokenizer *t);
+
 /* ---- single-cell input: read formats, barcode whitelist, barcode translation (ReadFormatter.hpp, BarcodeCorrector.hpp,
  * BarcodeTranslator.hpp; the flow of CentrifugerClass.cpp:163-224, :565-574) ----
  * Handles of their own, independent of any cfr_dev_index; one call at a time per handle.  Barcodes, reads and comments are flat
