@@ -1,6 +1,8 @@
 """--merge-readpair on the device (k_merge_decide / k_merge_write) against the host twin (cfr_merge_pairs, itself pinned to the
 reference's ReadPairMerger by tests/test_merge_host_cpu.py), the classify entries that run it as a pre-step against the reference's
-TSVs, and the command line.  -m gpu."""
+TSVs, and the command line.  The second fixture (tests/golden/merge_long) and the two seeded sweeps drive the kernels to their own
+units: plane words 1..8 and the funnel shift into the last one, the 512-base switch to the byte path, offsets and overlaps at
+multiples of 64, and every overlap length 32..600 exactly on the similarity threshold and one substitution past it.  -m gpu."""
 import gzip
 import os
 import subprocess
@@ -97,6 +99,13 @@ def test_device_merge_equals_reference_dump(dev, fmt):
     mf.check_against_dump(fmt, d.merge_pairs(p["b1"], p["o1"], p["b2"], p["o2"], p["q1"], p["q2"]))
 
 
+@pytest.mark.parametrize("fmt", ["fq", "fa"])
+def test_device_merge_equals_reference_dump_long(dev, fmt):
+    _, d = dev(1)
+    p = mf.pairs(fmt, "merge_long")
+    mf.check_against_dump(fmt, d.merge_pairs(p["b1"], p["o1"], p["b2"], p["o2"], p["q1"], p["q2"]), "merge_long")
+
+
 @pytest.mark.parametrize("with_qual", [True, False])
 def test_device_merge_equals_host_merge(dev, random_pairs, with_qual):
     _, d = dev(1)
@@ -129,20 +138,157 @@ def test_long_mates_take_the_byte_path(dev):
     _same(d.merge_pairs(b1, o1, b2, o2, q1, q2), want)
 
 
+EDGE_LENS = (63, 64, 65, 127, 128, 129, 255, 256, 257, 319, 320, 321, 447, 448, 449, 511, 512, 513, 514, 600, 1100)
+EDGE_OFFSETS = (0, 1, 63, 64, 65, 128, 191, 192, 448)
+EDGE_OVERLAPS = tuple(k + d for k in (64, 128, 192, 256, 320, 384, 448, 512) for d in (-1, 0, 1))
+
+
+def _edge_pairs(rng):
+    """every (len1, len2) of EDGE_LENS: the same fragment seen by both mates with the overlap K, or the true offset j, taken from the
+    word-edge values that fit, in the plain and in the read-through pass, and mates that have nothing in common; more rounds where
+    both mates are longer than the planes (16 length combinations only).  1 to 3 % substitutions, a twentieth of the pairs with N / lower case."""
+    r1s, r2s, q1s, q2s = [], [], [], []
+
+    def rnd(n):
+        return ACGT[rng.integers(0, 4, size=n)]
+
+    def put(r1, rc, tie):
+        i = len(r1s)
+        r1, rc = r1.copy(), rc.copy()
+        for r in (r1, rc):
+            m = rng.random(len(r)) < (0.005, 0.01, 0.015)[i % 3]      # per mate: 1, 2, 3 % between the two
+            r[m] = ACGT[rng.integers(0, 4, size=int(m.sum()))]
+            if i % 20 == 7:
+                a, n = int(rng.integers(0, len(r))), int(rng.integers(1, 9))
+                r[a:a + n] = ord("N") if i % 40 == 7 else np.frombuffer(bytes(r[a:a + n]).lower(), dtype=np.uint8)
+        q1, rcq = rng.integers(33, 74, size=len(r1)).astype(np.uint8), rng.integers(33, 74, size=len(rc)).astype(np.uint8)
+        if tie is not None and i % 3 == 0:                            # ties of both quality rules where the mates really align
+            a1, a2, K = tie
+            rcq[a2:a2 + K] = q1[a1:a1 + K] + (14 if i % 2 else 0)
+        r1s.append(r1); r2s.append(COMP[rc[::-1]]); q1s.append(q1); q2s.append(rcq[::-1].copy())
+
+    n = 0
+    for L1 in EDGE_LENS:
+        for L2 in EDGE_LENS:
+            rounds = 1 if min(L1, L2) <= 512 else 6
+            for _ in range(rounds):
+                n += 1
+                m = min(L1, L2)
+                f = rnd(L1 + L2 + 600)
+                # plain pass: r1 = f[:L1], rc(r2) = f[j:j + L2]
+                Ks = [k for k in EDGE_OVERLAPS if k <= m]
+                K = Ks[n % len(Ks)] if Ks else m
+                put(f[:L1], f[L1 - K:L1 - K + L2], (L1 - K, 0, K))
+                js = [j for j in EDGE_OFFSETS if 0 < j <= L1 - 33]
+                j = js[n % len(js)]
+                put(f[:L1], f[j:j + L2], (j, 0, min(L1 - j, L2)))
+                # read-through pass: a fragment of F bases, rc(r2) = j adapter bases + the fragment, r1 = the fragment + adapter
+                F = Ks[(n + 1) % len(Ks)] if Ks else m
+                put(np.concatenate([f[:F], rnd(L1 - F)]), np.concatenate([rnd(L2 - F), f[:F]]), (0, L2 - F, F))
+                js = [j for j in EDGE_OFFSETS if j <= L2 - 33]
+                j = js[(n + 2) % len(js)]
+                F = L2 - j
+                put(np.concatenate([f[:F], rnd(max(0, L1 - F))])[:L1], np.concatenate([rnd(j), f[:F]]), (0, j, min(F, L1)))
+                # nothing in common
+                put(f[:L1], f[L1 + 300:L1 + 300 + L2], None)
+                if max(L1, L2) > 512:
+                    put(rnd(L1), rnd(L2), None)
+    b1, o1 = _flat(r1s)
+    b2, o2 = _flat(r2s)
+    return b1, o1, _flat(q1s)[0], b2, o2, _flat(q2s)[0]
+
+
+@pytest.fixture(scope="module")
+def edge_pairs():
+    p = _edge_pairs(np.random.default_rng(20261019))
+    host = {True: capi.merge_pairs(p[0], p[1], p[3], p[4], p[2], p[5], threads=16),
+            False: capi.merge_pairs(p[0], p[1], p[3], p[4], threads=16)}
+    return p, host
+
+
+@pytest.mark.parametrize("with_qual", [True, False])
+def test_device_merge_equals_host_merge_at_the_word_edges(dev, edge_pairs, with_qual):
+    _, d = dev(1)
+    (b1, o1, q1, b2, o2, q2), host = edge_pairs
+    want = host[with_qual]
+    n = len(o1) - 1
+    assert 2000 <= n <= 4000
+    len1, len2 = np.diff(o1.astype(np.int64)), np.diff(o2.astype(np.int64))
+    longs = (len1 > 512).astype(int) + (len2 > 512)
+    for c, name in enumerate(("both at most 512", "mixed", "both above 512")):      # a kernel that never merges long pairs must fail
+        kinds = want["kind"][longs == c].tolist()
+        print(name, int((longs == c).sum()), "pairs, kinds 0/1/2:", [kinds.count(k) for k in (0, 1, 2)])
+        assert min(kinds.count(k) for k in (0, 1, 2)) >= 50, (name, [kinds.count(k) for k in (0, 1, 2)])
+    for shift in (0, 1, 2, 3, 5):                                  # the buffers' alignment
+        pad = np.full(shift, ord("G"), dtype=np.uint8)
+        sh = np.uint64(shift)
+        got = d.merge_pairs(np.concatenate([pad, b1]), o1 + sh, np.concatenate([pad, b2]), o2 + sh,
+                            np.concatenate([pad, q1]) if with_qual else None, np.concatenate([pad, q2]) if with_qual else None)
+        _same(got, want)
+
+
+THRESHOLD_LENGTHS = range(32, 601)
+
+
+def _threshold_geometry(L):
+    """offset j and the e bases behind the overlap: both mates within the 512 bases of the planes as long as L allows it (L <= 511),
+    j over 1..67 so that it is 64 and 65 for some L"""
+    j = 1 + L % 67
+    return (min(j, 512 - L), min(60, 512 - L)) if L < 512 else (j, 60)
+
+
+@pytest.fixture(scope="module")
+def threshold_pairs():
+    """per L four pairs: plain pass at L - T(L) substitutions and at one more, read-through pass the same; T from Python floats
+    (merge_fixtures.threshold).  Substitutions spread over the overlap's words for one pass and packed into its end for the other,
+    swapping with L."""
+    rng = np.random.default_rng(20261020)
+    r1s, r2s = [], []
+    for L in THRESHOLD_LENGTHS:
+        j, e = _threshold_geometry(L)
+        n = L - mf.threshold(L)
+        for rt in (False, True):
+            for extra in (0, 1):
+                r1, r2 = mf.threshold_pair(ACGT[rng.integers(0, 4, size=j + L + e)], L, rt, j, e, n + extra, bool(L & 1) != rt,
+                                           ACGT[rng.integers(0, 4, size=j + e)])
+                r1s.append(r1); r2s.append(r2)
+    b1, o1 = _flat(r1s)
+    b2, o2 = _flat(r2s)
+    q1, q2 = rng.integers(33, 74, size=len(b1)).astype(np.uint8), rng.integers(33, 74, size=len(b2)).astype(np.uint8)
+    return b1, o1, q1, b2, o2, q2
+
+
+def test_device_merge_on_the_similarity_threshold(dev, threshold_pairs):
+    """an offset passes iff L - mism >= int(L * t(L)): for every L in 32..600 the last number of substitutions that merges and the
+    first that does not, in both passes - first that the host twin does as designed (so that the comparison is not between two
+    empty answers), then device == twin on every field"""
+    _, d = dev(1)
+    b1, o1, q1, b2, o2, q2 = threshold_pairs
+    assert len(o1) - 1 == 4 * 569
+    for quals in ((q1, q2), (None, None)):
+        want = capi.merge_pairs(b1, o1, b2, o2, quals[0], quals[1], threads=16)
+        kind, ov, off = want["kind"].reshape(-1, 4), want["overlap"].reshape(-1, 4), want["offset"].reshape(-1, 4)
+        Ls = np.array(THRESHOLD_LENGTHS)
+        js = np.array([_threshold_geometry(L)[0] for L in THRESHOLD_LENGTHS])
+        assert np.array_equal(kind, np.tile([1, 0, 2, 0], (len(Ls), 1))), np.nonzero((kind != [1, 0, 2, 0]).any(axis=1))[0] + 32
+        assert np.array_equal(ov[:, 0], Ls) and np.array_equal(ov[:, 2], Ls) and (ov[:, [1, 3]] == -1).all()
+        assert np.array_equal(off[:, 0], js) and np.array_equal(off[:, 2], js) and (off[:, [1, 3]] == -1).all()
+        _same(d.merge_pairs(b1, o1, b2, o2, quals[0], quals[1]), want)
+
+
 def _tsv(idx, ids, results, matches):
     return capi.tsv_header() + b"".join(idx.format_tsv(ids[i].decode(), results[i], matches) for i in range(len(ids)))
 
 
-@pytest.mark.parametrize("case", ["fq_k1", "fq_k5", "fq_nodust", "fa_k1"])
-def test_classify_merged_equals_reference_tsv(dev, case):
+def _classify_merged_case(dev, case, which):
     import torch
-    args = mf.manifest()["cases"][case]["args"]
+    args = mf.manifest(which)["cases"][case]["args"]
     fmt = "fq" if case.startswith("fq") else "fa"
     k = int(args[args.index("-k") + 1]) if "-k" in args else 1
     idx, d = dev(k)
-    p = mf.pairs(fmt)
-    kinds = np.array([r[0] for r in mf.dump(fmt)], dtype=np.int32)
-    want = mf.tsv(case)
+    p = mf.pairs(fmt, which)
+    kinds = np.array([r[0] for r in mf.dump(fmt, which)], dtype=np.int32)
+    want = mf.tsv(case, which)
     d.set_merge(True)
     try:
         # SDUST on the device behind the merge
@@ -162,7 +308,7 @@ def test_classify_merged_equals_reference_tsv(dev, case):
         # SDUST off on the device: the host masks the merged reads, the device classifies them as they are (merge off)
         d.set_dust(False)
         if "--no-dust" not in args:
-            b1, o1, _, b2, o2, _ = mf.expected_reads(fmt)
+            b1, o1, _, b2, o2, _ = mf.expected_reads(fmt, which)
             b1, b2 = b1.copy(), b2.copy()
             capi.dust_mask(b1, o1); capi.dust_mask(b2, o2)
             d.set_merge(False)
@@ -171,6 +317,16 @@ def test_classify_merged_equals_reference_tsv(dev, case):
     finally:
         d.set_dust(False)
         d.set_merge(False)
+
+
+@pytest.mark.parametrize("case", ["fq_k1", "fq_k5", "fq_nodust", "fa_k1"])
+def test_classify_merged_equals_reference_tsv(dev, case):
+    _classify_merged_case(dev, case, "merge")
+
+
+@pytest.mark.parametrize("case", ["fq_k1", "fq_nodust", "fa_k1"])
+def test_classify_merged_equals_reference_tsv_long(dev, case):
+    _classify_merged_case(dev, case, "merge_long")
 
 
 def test_empty_mate_equals_single_end(dev):
@@ -231,12 +387,12 @@ def test_single_end_packed_and_protein(dev, golden_dir):
         pd.close()
 
 
-def _cli(tmp_path, golden_dir, fmt, extra):
+def _cli(tmp_path, golden_dir, fmt, extra, which="merge"):
     files = []
     for m in (1, 2):
-        f = tmp_path / f"pairs_{m}.{fmt}"
+        f = tmp_path / (f"pairs_{m}.{fmt}" if which == "merge" else f"{which}_{m}.{fmt}")
         if not f.exists():
-            f.write_bytes(gzip.open(os.path.join(mf.MERGE, f"pairs_{m}.{fmt}.gz"), "rb").read())
+            f.write_bytes(gzip.open(os.path.join(mf.GOLDEN, which, f"pairs_{m}.{fmt}.gz"), "rb").read())
         files.append(str(f))
     exe = os.path.join(ROOT, "centrifuger_amd", "bin", "centrifuger")
     r = subprocess.run([exe, "-x", os.path.join(golden_dir, "f6"), "-1", files[0], "-2", files[1], "--merge-readpair"] + extra,
@@ -252,6 +408,15 @@ def test_cli_merge_readpair_equals_reference(tmp_path, golden_dir, case):
     assert _cli(tmp_path, golden_dir, fmt, args) == mf.tsv(case)
     if case == "fq_k5":                                        # merged and unmerged pairs on both sides of every batch boundary
         assert _cli(tmp_path, golden_dir, fmt, args + ["--gpu-batch", "256"]) == mf.tsv(case)
+
+
+@pytest.mark.parametrize("case", ["fq_k1", "fq_nodust", "fa_k1"])
+def test_cli_merge_readpair_equals_reference_long(tmp_path, golden_dir, case):
+    args = mf.manifest("merge_long")["cases"][case]["args"][4:]
+    fmt = "fq" if case.startswith("fq") else "fa"
+    assert _cli(tmp_path, golden_dir, fmt, args, "merge_long") == mf.tsv(case, "merge_long")
+    if case == "fq_k1":                                        # merged and unmerged long pairs on both sides of every batch boundary
+        assert _cli(tmp_path, golden_dir, fmt, args + ["--gpu-batch", "64"], "merge_long") == mf.tsv(case, "merge_long")
 
 
 @pytest.mark.parametrize("batch", [[], ["--gpu-batch", "256"]])
