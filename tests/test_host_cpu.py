@@ -227,7 +227,7 @@ def test_tail_slices_with_more_threads_than_reads(golden_dir):
     assert len(m1) >= 1 and int(r1["n_match"].sum()) == len(m1)
 
 
-def test_cli_rejects_out_of_scope_options_and_missing_index(golden_dir):
+def test_cli_rejects_out_of_scope_options_and_missing_index(golden_dir, tmp_path):
     """The drop-in command line refuses options outside the path and reports a missing index as an error, both before
     any device work (so this runs without a GPU)."""
     import subprocess
@@ -241,6 +241,10 @@ def test_cli_rejects_out_of_scope_options_and_missing_index(golden_dir):
     assert r.returncode != 0 and b"loading the index" in r.stderr
     r = subprocess.run([cli], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     assert r.returncode == 0 and b"-x FILE: index prefix" in r.stderr       # no arguments: usage, exit 0 (like the reference's CI smoke)
+    # an option out of range is refused with the other options, before the index is opened or any thread starts
+    r = subprocess.run([cli, "-x", "unused", "-u", os.path.join(golden_dir, "se.fq"), "--quant", str(tmp_path / "report.tsv"), "--quant-format", "9"],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert r.returncode == 1 and b"--quant-format takes 0, 1, 2 or 3." in r.stderr and r.stdout == b""
     if capi.device_count() == 0:
         r = subprocess.run([cli, "-x", os.path.join(golden_dir, "f6"), "-u", os.path.join(golden_dir, "se.fq")], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
         assert r.returncode != 0 and b"no CPU fallback" in r.stderr
@@ -302,6 +306,26 @@ def _py_parse(data: bytes):
     return recs
 
 
+def _dna(rng, n):
+    return bytes(rng.choice(list(b"ACGTN"), size=n, p=[.24, .24, .24, .24, .04]).astype(np.uint8))
+
+
+_rng = np.random.default_rng(5)
+# awkward inputs of the command line's read parser (test_cli_read_parser here, tests/test_reads_sanitized_cpu.py under the sanitizers)
+CASES = {
+    "fastq4": b"".join(b"@r%d/1 desc x\n%s\n+\n%s\n" % (i, _dna(_rng, 50 + i), b"I" * (50 + i)) for i in range(200)),
+    "fastq_at_quality": b"@a\nACGT\n+\n@@@@\n@b extra\nGGCC\n+b\n@III\n",
+    "fasta_multiline_crlf": b">s1 first\r\nACGT\r\nGGTT\r\n\r\n>s2\r\nTTTT\r\n",
+    "fasta_no_trailing_newline": b">x\nACGTACGT\n>y/2\nGGG",
+    "fastq_multiline": b"@m1\nACGT\nACGT\n+\nIIII\nIIII\n@m2\nAC\n+\nII\n",
+    "mixed_blank": b"\n\n>f1\nAC\n\nGT\n@q1\nAAAA\n+\nIIII\n>f2\nCC\n",
+    "long_record": b">big\n" + b"\n".join(_dna(_rng, 70) for _ in range(3000)) + b"\n>tail\nACGT\n",
+    "fastq_empty_sequence": b"@e1\n@e2\nACGT\n+\nIIII\n@e3\n+\n\n@e4\nGG\n+\nII\n",
+    "fasta_with_plus_line": b">f\nACGT\n+\nIIII\n>g\nCC\n",
+    "huge_line": b">one\n" + _dna(_rng, 400_000) + b"\n>two\nAC\n",       # (test_cli_read_parser: 40 000 000 bases in the plain file)
+}
+
+
 @pytest.mark.parametrize("gz", [False, True])
 def test_cli_read_parser(tmp_path, gz):
     """The block parser of the command line (CFR_CLI_PARSE_ONLY hook: no index, no device) on awkward inputs."""
@@ -310,22 +334,13 @@ def test_cli_read_parser(tmp_path, gz):
     cli = os.path.join(ROOT, "centrifuger_amd", "bin", "centrifuger")
     if not os.path.exists(cli):
         pytest.skip("CLI not built")
-    rng = np.random.default_rng(5)
+    cases = dict(CASES)
+    if not gz:
+        cases["huge_line"] = b">one\n" + _dna(np.random.default_rng(7), 40_000_000) + b"\n>two\nAC\n"
+    rng = np.random.default_rng(6)
 
     def dna(n):
-        return bytes(rng.choice(list(b"ACGTN"), size=n, p=[.24, .24, .24, .24, .04]).astype(np.uint8))
-    cases = {
-        "fastq4": b"".join(b"@r%d/1 desc x\n%s\n+\n%s\n" % (i, dna(50 + i), b"I" * (50 + i)) for i in range(200)),
-        "fastq_at_quality": b"@a\nACGT\n+\n@@@@\n@b extra\nGGCC\n+b\n@III\n",
-        "fasta_multiline_crlf": b">s1 first\r\nACGT\r\nGGTT\r\n\r\n>s2\r\nTTTT\r\n",
-        "fasta_no_trailing_newline": b">x\nACGTACGT\n>y/2\nGGG",
-        "fastq_multiline": b"@m1\nACGT\nACGT\n+\nIIII\nIIII\n@m2\nAC\n+\nII\n",
-        "mixed_blank": b"\n\n>f1\nAC\n\nGT\n@q1\nAAAA\n+\nIIII\n>f2\nCC\n",
-        "long_record": b">big\n" + b"\n".join(dna(70) for _ in range(3000)) + b"\n>tail\nACGT\n",
-        "fastq_empty_sequence": b"@e1\n@e2\nACGT\n+\nIIII\n@e3\n+\n\n@e4\nGG\n+\nII\n",
-        "fasta_with_plus_line": b">f\nACGT\n+\nIIII\n>g\nCC\n",
-        "huge_line": b">one\n" + dna(40_000_000 if not gz else 400_000) + b"\n>two\nAC\n",
-    }
+        return _dna(rng, n)
     for name, data in cases.items():
         path = tmp_path / (name + (".gz" if gz else ".txt"))
         if gz:
