@@ -104,6 +104,9 @@ EXPORTS = [
     "cfr_taxonomy_open", "cfr_taxonomy_get_tables", "cfr_taxonomy_tax_name", "cfr_taxonomy_seq_name", "cfr_tax_rank_string", "cfr_taxonomy_close",
     "cfr_promote_open", "cfr_promote_apply", "cfr_promote_lca_warnings", "cfr_promote_get_stats", "cfr_promote_close",
     "cfr_device_index_set_promote", "cfr_last_promote_ms",
+    "cfr_kreport_options_default", "cfr_kreport_open", "cfr_kreport_add_results", "cfr_kreport_add_tsv", "cfr_kreport_add_count_table",
+    "cfr_kreport_add_counts", "cfr_kreport_bins", "cfr_kreport_counts", "cfr_kreport_warnings", "cfr_kreport_write", "cfr_kreport_get_stats",
+    "cfr_kreport_close", "cfr_kreport_scan_warnings", "cfr_device_index_set_kreport", "cfr_device_index_kreport_counts", "cfr_last_kreport_ms",
     "cfr_tokenizer_open", "cfr_tokenize", "cfr_tokenizer_fetch", "cfr_tokenizer_device_reads", "cfr_tokenizer_get_stats", "cfr_tokenizer_close",
 ]
 
@@ -131,7 +134,7 @@ def lib():
                             "cfr_quant_options_default", "cfr_quant_destroy", "cfr_read_format_destroy", "cfr_barcode_destroy",
                             "cfr_barcode_translate_destroy", "cfr_tsv_header_ex", "cfr_format_tsv_ex",
                             "cfr_taxonomy_tax_name", "cfr_taxonomy_seq_name", "cfr_tax_rank_string", "cfr_taxonomy_close",
-                            "cfr_tokenizer_close"):
+                            "cfr_tokenizer_close", "cfr_kreport_options_default"):
                 getattr(L, name).restype = C.c_int
         for name in ("cfr_quant_destroy", "cfr_read_format_destroy", "cfr_barcode_destroy", "cfr_barcode_translate_destroy"):
             getattr(L, name).restype = None
@@ -432,6 +435,27 @@ class DeviceIndex:
         """cfr_device_index_set_promote: every following wide classify call promotes its results to `level` ("lca" or a rank string) in
         HBM before they are copied out; None switches it off"""
         _check(lib().cfr_device_index_set_promote(self._d, None if level is None else level.encode()))
+
+    def set_kreport(self, on=True, **options):
+        """cfr_device_index_set_kreport: every following wide classify call counts its reads into the image's bins (options as
+        kreport_options(); on=False switches it off).  Switching it on zeroes the bins."""
+        if not on:
+            _check(lib().cfr_device_index_set_kreport(self._d, None))
+            return
+        o = kreport_options(**options)
+        _check(lib().cfr_device_index_set_kreport(self._d, C.byref(o)))
+
+    def kreport_counts(self, bins: int):
+        """(own, own_score, seq_count) of the image's bins; bins = node_cnt + 1 (Kreport.bins)"""
+        own, sc = np.zeros(bins, dtype=np.uint64), np.zeros(bins, dtype=np.uint64)
+        seq = C.c_double(0)
+        _check(lib().cfr_device_index_kreport_counts(self._d, _p(own), _p(sc), C.c_size_t(bins), C.byref(seq)))
+        return own, sc, seq.value
+
+    def last_kreport_ms(self) -> float:
+        ms = C.c_float(0)
+        _check(lib().cfr_last_kreport_ms(self._d, C.byref(ms)))
+        return ms.value
 
     def last_promote_ms(self) -> float:
         ms = C.c_float(0)
@@ -890,6 +914,92 @@ class Promote:
     def close(self):
         if self._h:
             lib().cfr_promote_close(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class KreportOptions(C.Structure):
+    _fields_ = [("has_min_score", C.c_int32), ("has_min_length", C.c_int32), ("min_score", C.c_uint64), ("min_length", C.c_int64),
+                ("no_lca", C.c_int32), ("show_zeros", C.c_int32), ("score_data", C.c_int32), ("max_blocks", C.c_uint32), ("lds_slots", C.c_uint32),
+                ("threads", C.c_int32), ("pad", C.c_int32)]
+
+
+class KreportStats(C.Structure):
+    _fields_ = [("fold_ms", C.c_float), ("accumulate_ms", C.c_float), ("parse_ms", C.c_float)]
+
+
+def kreport_options(min_score=None, min_length=None, no_lca=False, show_zeros=False, score_data=False, max_blocks=0, lds_slots=0, threads=0) -> KreportOptions:
+    o = KreportOptions()
+    lib().cfr_kreport_options_default(C.byref(o))
+    if min_score is not None:
+        o.has_min_score, o.min_score = 1, min_score
+    if min_length is not None:
+        o.has_min_length, o.min_length = 1, min_length
+    o.no_lca, o.show_zeros, o.score_data, o.max_blocks, o.lds_slots, o.threads = int(no_lca), int(show_zeros), int(score_data), max_blocks, lds_slots, threads
+    return o
+
+
+class Kreport:
+    """cfr_kreport: centrifuger-kreport, reads counted per taxon.  Options as kreport_options().  device=None: the host twin, no GPU is
+    touched.  Bins: node_cnt + 1, the compact nodes and then "unclassified"."""
+
+    def __init__(self, prefix: str, device=0, **options):
+        self._h = C.c_void_p()
+        o = kreport_options(**options)
+        _check(lib().cfr_kreport_open(prefix.encode(), C.byref(o), C.c_int(-1 if device is None else device), C.byref(self._h)))
+        n = C.c_size_t(0)
+        _check(lib().cfr_kreport_bins(self._h, C.byref(n)))
+        self.bins = n.value
+
+    def add_results(self, results, matches):
+        assert results.dtype == RESULT_DTYPE and matches.dtype == MATCH_DTYPE and results.flags.c_contiguous and matches.flags.c_contiguous
+        _check(lib().cfr_kreport_add_results(self._h, _p(results), _p(matches), C.c_size_t(len(results))))
+
+    def add_tsv(self, path: str):
+        _check(lib().cfr_kreport_add_tsv(self._h, path.encode()))
+
+    def add_count_table(self, path: str):
+        _check(lib().cfr_kreport_add_count_table(self._h, path.encode()))
+
+    def add_counts(self, own, own_score=None):
+        own, own_score = _u64(own), _u64(own_score)
+        _check(lib().cfr_kreport_add_counts(self._h, _p(own), _p(own_score), C.c_size_t(len(own))))
+
+    def counts(self):
+        """(own, clade, own_score, clade_score, seq_count)"""
+        a = [np.zeros(self.bins, dtype=np.uint64) for _ in range(4)]
+        seq = C.c_double(0)
+        _check(lib().cfr_kreport_counts(self._h, _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), C.c_size_t(self.bins), C.byref(seq)))
+        return a[0], a[1], a[2], a[3], seq.value
+
+    def warnings(self):
+        """tax ids of the script's "Couldn't find parent of taxID" lines for everything added so far, in its order"""
+        n = C.c_size_t(0)
+        st = lib().cfr_kreport_warnings(self._h, None, C.c_size_t(0), C.byref(n))
+        if st == CFR_OK:
+            return np.zeros(0, dtype=np.uint64)
+        if st != CFR_ERR_CAPACITY:
+            _check(st)
+        out = np.zeros(n.value, dtype=np.uint64)
+        _check(lib().cfr_kreport_warnings(self._h, _p(out), C.c_size_t(len(out)), C.byref(n)))
+        return out
+
+    def write(self, path=None):
+        _check(lib().cfr_kreport_write(self._h, None if path is None else path.encode()))
+
+    def stats(self) -> KreportStats:
+        st = KreportStats()
+        _check(lib().cfr_kreport_get_stats(self._h, C.byref(st)))
+        return st
+
+    def close(self):
+        if self._h:
+            lib().cfr_kreport_close(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -16,6 +16,7 @@
 #include "cfr_barcode.hpp"
 #include "cfr_build.hpp"
 #include "cfr_device.hpp"
+#include "cfr_kreport.hpp"
 #include "cfr_promote.hpp"
 #include "cfr_quant.hpp"
 #include "cfr_tail.hpp"
@@ -33,6 +34,7 @@ struct cfr_taxonomy {
   std::vector<uint64_t> taxid_length, length_seq_id, length_value;
 };
 struct cfr_promote { cfr::Promote *p; };
+struct cfr_kreport { cfr::Kreport *k; };
 struct cfr_tokenizer { cfr::Tokenizer *t; };
 struct cfr_quant { cfr::Quant *q; std::vector<double> weight; int32_t rounds = 0; bool ran = false; };
 // One call at a time per device image: `busy` is held for the length of every entry that touches the image (try_lock:
@@ -80,6 +82,14 @@ std::set<const cfr_promote *> g_promote_live;
 bool promote_live(const cfr_promote *h) {
   std::lock_guard<std::mutex> lk(g_promote_mu);
   return h && g_promote_live.count(h) != 0;
+}
+
+// ... the cfr_kreport handles
+std::mutex g_kreport_mu;
+std::set<const cfr_kreport *> g_kreport_live;
+bool kreport_live(const cfr_kreport *h) {
+  std::lock_guard<std::mutex> lk(g_kreport_mu);
+  return h && g_kreport_live.count(h) != 0;
 }
 
 // ... and the cfr_tokenizer handles
@@ -356,6 +366,7 @@ cfr_status cfr_classify_batch_expanded(cfr_dev_index *d, const uint8_t *bases1, 
   if ((bases2 == nullptr) != (offsets2 == nullptr)) return bad_arg("cfr_classify_batch_expanded: bases2/offsets2 must both be given");
   if (!d->d->host().params.output_expanded) return bad_arg("cfr_classify_batch_expanded: the index was opened without cfr_params.output_expanded");
   if (d->d->promote()) return bad_arg("cfr_classify_batch_expanded: promotion is switched on (cfr_device_index_set_promote) and does not cover the expanded lists");
+  if (d->d->kreport()) return bad_arg("cfr_classify_batch_expanded: the report is switched on (cfr_device_index_set_kreport) and is made by the wide entries only");
   CFR_ENTER(d, "cfr_classify_batch_expanded");
   return guarded([&]() -> cfr_status {
     d->d->classify_host(bases1, offsets1, bases2, offsets2, n, results, matches, match_cap, n_matches);
@@ -463,6 +474,7 @@ cfr_status cfr_classify_batch_resident_compact(cfr_dev_index *d, const void *d_b
   if (!d || (n && (!d_bases1 || !d_offsets1 || !results || !matches))) return bad_arg("cfr_classify_batch_resident_compact: null argument");
   if ((d_bases2 == nullptr) != (d_offsets2 == nullptr)) return bad_arg("cfr_classify_batch_resident_compact: mate buffers must both be given");
   if (d->d->promote()) return bad_arg("cfr_classify_batch_resident_compact: promotion is switched on (cfr_device_index_set_promote) and works on the wide layout: use cfr_classify_batch_resident");
+  if (d->d->kreport()) return bad_arg("cfr_classify_batch_resident_compact: the report is switched on (cfr_device_index_set_kreport) and works on the wide layout: use cfr_classify_batch_resident");
   CFR_ENTER(d, "cfr_classify_batch_resident_compact");
   return guarded([&]() -> cfr_status {
     d->d->classify_device((const uint8_t *)d_bases1, (const uint64_t *)d_offsets1, (const uint8_t *)d_bases2,
@@ -803,6 +815,144 @@ cfr_status cfr_device_index_set_promote(cfr_dev_index *d, const char *level) {
 cfr_status cfr_last_promote_ms(const cfr_dev_index *d, float *ms) {
   if (!d || !ms) return bad_arg("cfr_last_promote_ms: null argument");
   *ms = d->d->last_promote_ms;
+  return CFR_OK;
+}
+
+// ---- centrifuger-kreport ----
+void cfr_kreport_options_default(cfr_kreport_options *o) {
+  if (o) memset(o, 0, sizeof(*o));
+}
+
+cfr_status cfr_kreport_open(const char *idx_prefix, const cfr_kreport_options *opts, int device, cfr_kreport **out) {
+  if (!idx_prefix || !opts || !out) return bad_arg("cfr_kreport_open: null argument");
+  *out = nullptr;
+  if (device < -1) return bad_arg("cfr_kreport_open: device is a HIP ordinal, or -1 for the host twin");
+  if (opts->lds_slots && (opts->lds_slots < 64 || opts->lds_slots > 2048 || (opts->lds_slots & (opts->lds_slots - 1))))
+    return bad_arg("cfr_kreport_open: lds_slots is 0 or a power of two in [64, 2048]");
+  return guarded([&]() -> cfr_status {
+    cfr::KreportOptions o;
+    o.has_min_score = opts->has_min_score != 0; o.has_min_length = opts->has_min_length != 0;
+    o.min_score = opts->min_score; o.min_length = opts->min_length;
+    o.no_lca = opts->no_lca != 0; o.show_zeros = opts->show_zeros != 0; o.score_data = opts->score_data != 0;
+    std::unique_ptr<cfr_kreport> h(new cfr_kreport{nullptr});
+    h->k = new cfr::Kreport(idx_prefix, o, device, opts->max_blocks, opts->lds_slots, opts->threads);
+    { std::lock_guard<std::mutex> lk(g_kreport_mu); g_kreport_live.insert(h.get()); }
+    *out = h.release();
+    return CFR_OK;
+  });
+}
+
+cfr_status cfr_kreport_add_results(cfr_kreport *h, const cfr_result *results, const cfr_match *matches, size_t n) {
+  if (!kreport_live(h)) return bad_arg("cfr_kreport_add_results: not an open cfr_kreport handle");
+  if (n && !results) return bad_arg("cfr_kreport_add_results: null argument");
+  for (size_t i = 0; i < n; ++i) {
+    if (results[i].n_match > 0 && !matches) return bad_arg("cfr_kreport_add_results: null argument");
+    if (results[i].n_match > 0 && results[i].match_begin + (uint64_t)results[i].n_match < results[i].match_begin) return bad_arg("cfr_kreport_add_results: match_begin + n_match wraps");
+  }
+  return guarded([&]() -> cfr_status { h->k->add_results(results, matches, n); return CFR_OK; });
+}
+
+cfr_status cfr_kreport_scan_warnings(cfr_kreport *h, const cfr_result *results, const cfr_match *matches, size_t n) {
+  if (!kreport_live(h)) return bad_arg("cfr_kreport_scan_warnings: not an open cfr_kreport handle");
+  if (n && !results) return bad_arg("cfr_kreport_scan_warnings: null argument");
+  for (size_t i = 0; i < n; ++i) if (results[i].n_match > 0 && !matches) return bad_arg("cfr_kreport_scan_warnings: null argument");
+  return guarded([&]() -> cfr_status { h->k->scan_warnings(results, matches, n); return CFR_OK; });
+}
+
+cfr_status cfr_kreport_add_tsv(cfr_kreport *h, const char *path) {
+  if (!kreport_live(h)) return bad_arg("cfr_kreport_add_tsv: not an open cfr_kreport handle");
+  if (!path) return bad_arg("cfr_kreport_add_tsv: null argument");
+  return guarded([&]() -> cfr_status { h->k->add_tsv(path); return CFR_OK; });
+}
+
+cfr_status cfr_kreport_add_count_table(cfr_kreport *h, const char *path) {
+  if (!kreport_live(h)) return bad_arg("cfr_kreport_add_count_table: not an open cfr_kreport handle");
+  if (!path) return bad_arg("cfr_kreport_add_count_table: null argument");
+  return guarded([&]() -> cfr_status { h->k->add_count_table(path); return CFR_OK; });
+}
+
+cfr_status cfr_kreport_add_counts(cfr_kreport *h, const uint64_t *own, const uint64_t *own_score, size_t n) {
+  if (!kreport_live(h)) return bad_arg("cfr_kreport_add_counts: not an open cfr_kreport handle");
+  if (!own) return bad_arg("cfr_kreport_add_counts: null argument");
+  return guarded([&]() -> cfr_status { h->k->add_counts(own, own_score, n); return CFR_OK; });
+}
+
+cfr_status cfr_kreport_bins(cfr_kreport *h, size_t *n) {
+  if (!kreport_live(h)) return bad_arg("cfr_kreport_bins: not an open cfr_kreport handle");
+  if (!n) return bad_arg("cfr_kreport_bins: null argument");
+  *n = (size_t)h->k->bins();
+  return CFR_OK;
+}
+
+cfr_status cfr_kreport_counts(cfr_kreport *h, uint64_t *own, uint64_t *clade, uint64_t *own_score, uint64_t *clade_score, size_t cap, double *seq_count) {
+  if (!kreport_live(h)) return bad_arg("cfr_kreport_counts: not an open cfr_kreport handle");
+  if (!seq_count) return bad_arg("cfr_kreport_counts: null argument");
+  if ((own || clade || own_score || clade_score) && cap < h->k->bins()) { g_err = "cfr_kreport_counts: the arrays take node_cnt + 1 entries"; return CFR_ERR_CAPACITY; }
+  return guarded([&]() -> cfr_status {
+    std::vector<uint64_t> a, b, c, d;
+    h->k->counts(a, b, c, d, *seq_count);
+    if (own) memcpy(own, a.data(), a.size() * 8);
+    if (clade) memcpy(clade, b.data(), b.size() * 8);
+    if (own_score) memcpy(own_score, c.data(), c.size() * 8);
+    if (clade_score) memcpy(clade_score, d.data(), d.size() * 8);
+    return CFR_OK;
+  });
+}
+
+cfr_status cfr_kreport_warnings(cfr_kreport *h, uint64_t *taxids, size_t cap, size_t *count) {
+  if (!kreport_live(h)) return bad_arg("cfr_kreport_warnings: not an open cfr_kreport handle");
+  if (!count || (cap && !taxids)) return bad_arg("cfr_kreport_warnings: null argument");
+  const std::vector<uint64_t> &w = h->k->warnings();
+  *count = w.size();
+  if (w.size() > cap) { g_err = "cfr_kreport_warnings: tax id buffer too small"; return CFR_ERR_CAPACITY; }
+  if (!w.empty()) memcpy(taxids, w.data(), w.size() * 8);
+  return CFR_OK;
+}
+
+cfr_status cfr_kreport_write(cfr_kreport *h, const char *path) {
+  if (!kreport_live(h)) return bad_arg("cfr_kreport_write: not an open cfr_kreport handle");
+  return guarded([&]() -> cfr_status { h->k->write(path); return CFR_OK; });     // (nothing counted: std::runtime_error -> CFR_ERR_ARG with the script's message)
+}
+
+cfr_status cfr_device_index_set_kreport(cfr_dev_index *d, const cfr_kreport_options *opts) {
+  if (!d) return bad_arg("cfr_device_index_set_kreport: null argument");
+  CFR_ENTER(d, "cfr_device_index_set_kreport");
+  return guarded([&]() -> cfr_status {
+    if (!opts) { d->d->set_kreport(nullptr); return CFR_OK; }
+    cfr::KreportOptions o;
+    o.has_min_score = opts->has_min_score != 0; o.has_min_length = opts->has_min_length != 0;
+    o.min_score = opts->min_score; o.min_length = opts->min_length;
+    o.no_lca = opts->no_lca != 0; o.show_zeros = opts->show_zeros != 0; o.score_data = opts->score_data != 0;
+    d->d->set_kreport(&o);
+    return CFR_OK;
+  });
+}
+cfr_status cfr_device_index_kreport_counts(cfr_dev_index *d, uint64_t *own, uint64_t *own_score, size_t cap, double *seq_count) {
+  if (!d) return bad_arg("cfr_device_index_kreport_counts: null argument");
+  CFR_ENTER(d, "cfr_device_index_kreport_counts");
+  if ((own || own_score) && cap < d->d->kreport_bins()) { g_err = "cfr_device_index_kreport_counts: the arrays take node_cnt + 1 entries"; return CFR_ERR_CAPACITY; }
+  return guarded([&]() -> cfr_status { d->d->kreport_counts(own, own_score, seq_count); return CFR_OK; });
+}
+cfr_status cfr_last_kreport_ms(const cfr_dev_index *d, float *ms) {
+  if (!d || !ms) return bad_arg("cfr_last_kreport_ms: null argument");
+  *ms = d->d->last_kreport_ms;
+  return CFR_OK;
+}
+
+cfr_status cfr_kreport_get_stats(cfr_kreport *h, cfr_kreport_stats *st) {
+  if (!kreport_live(h)) return bad_arg("cfr_kreport_get_stats: not an open cfr_kreport handle");
+  if (!st) return bad_arg("cfr_kreport_get_stats: null argument");
+  st->fold_ms = h->k->fold_ms(); st->accumulate_ms = h->k->accumulate_ms(); st->parse_ms = h->k->parse_ms();
+  return CFR_OK;
+}
+
+cfr_status cfr_kreport_close(cfr_kreport *h) {
+  {
+    std::lock_guard<std::mutex> lk(g_kreport_mu);
+    if (!h || !g_kreport_live.erase(h)) return bad_arg("cfr_kreport_close: not an open cfr_kreport handle");
+  }
+  delete h->k;
+  delete h;
   return CFR_OK;
 }
 

@@ -58,6 +58,9 @@ const char *kUsage =
     "\t--promote STR: promote every assignment to the rank <str> (genus, species, ...), or merge a read's assignments into their lowest\n"
     "\t\tcommon ancestor (lca), on the GPU before the rows are written (equal to centrifuger-promote IDX this-output-without-it STR when no two\n"
     "\t\tadjacent reads share a read id); not together with --quant or --expand-taxid [no promotion]\n"
+    "\t--kreport FILE: also write the Kraken-style report of centrifuger-kreport for this run to FILE, the reads counted per taxon on the GPU\n"
+    "\t\t(equal to centrifuger-kreport -x IDX this-output-without---promote); with --gpu LIST every GPU counts its own reads and the counts\n"
+    "\t\tare summed after the last batch; not together with --expand-taxid [no report]\n"
     "\t--gpu LIST: comma separated MI355X ordinals, or 'all' [0]\n"
     "\t--gpu-batch INT: reads per device batch [262144]\n"
     "\t--gpu-balanced: also derive the text-mode tables and the locate memo on the device (+0.4 s load per Gbp, faster kernels)\n"
@@ -67,7 +70,7 @@ const char *kUsage =
     "\t-h: print this usage message\n"
     "\t-v: print the version information and quit\n";
 
-enum { OPT_UN = 1000, OPT_CL, OPT_NO_DUST, OPT_MIN_HITLEN, OPT_HITK, OPT_SECONDARY, OPT_GPU, OPT_GPU_BATCH, OPT_GPU_THROUGHPUT, OPT_GPU_FASTLOAD, OPT_GPU_BALANCED, OPT_PARSE_THREADS, OPT_GPU_PARSE, OPT_EXPAND_TAXID, OPT_MERGE_READPAIR, OPT_QUANT, OPT_QUANT_FORMAT, OPT_PROMOTE, OPT_BARCODE, OPT_UMI, OPT_READ_FORMAT, OPT_BARCODE_WHITELIST, OPT_BARCODE_TRANSLATE, OPT_UNSUPPORTED };
+enum { OPT_UN = 1000, OPT_CL, OPT_NO_DUST, OPT_MIN_HITLEN, OPT_HITK, OPT_SECONDARY, OPT_GPU, OPT_GPU_BATCH, OPT_GPU_THROUGHPUT, OPT_GPU_FASTLOAD, OPT_GPU_BALANCED, OPT_PARSE_THREADS, OPT_GPU_PARSE, OPT_EXPAND_TAXID, OPT_MERGE_READPAIR, OPT_QUANT, OPT_QUANT_FORMAT, OPT_PROMOTE, OPT_KREPORT, OPT_BARCODE, OPT_UMI, OPT_READ_FORMAT, OPT_BARCODE_WHITELIST, OPT_BARCODE_TRANSLATE, OPT_UNSUPPORTED };
 
 // Persistent workers for the dust and the format stage: a 256 k-read batch is 6 ms of work on 64 threads, less than
 // what starting 64 threads costs, so the threads are started once.
@@ -129,6 +132,7 @@ struct Options {
   bool merge = false;                  // --merge-readpair
   std::string quant_path;              // --quant: the abundance report of this run
   int quant_format = 0;                // --quant-format
+  std::string kreport_path;            // --kreport: the Kraken-style report of this run
   std::string promote;                 // --promote: the level
   bool has_promote = false;
   std::string un_prefix, cl_prefix;
@@ -257,7 +261,7 @@ int parse_options(int argc, char *argv[], Options &opt) {
       {"parse-threads", required_argument, 0, OPT_PARSE_THREADS}, {"gpu-parse", no_argument, 0, OPT_GPU_PARSE},
       {"sample-sheet", required_argument, 0, OPT_UNSUPPORTED}, {"merge-readpair", no_argument, 0, OPT_MERGE_READPAIR},
       {"quant", required_argument, 0, OPT_QUANT}, {"quant-format", required_argument, 0, OPT_QUANT_FORMAT},
-      {"promote", required_argument, 0, OPT_PROMOTE},
+      {"promote", required_argument, 0, OPT_PROMOTE}, {"kreport", required_argument, 0, OPT_KREPORT},
       {"expand-taxid", no_argument, 0, OPT_EXPAND_TAXID}, {"read-format", required_argument, 0, OPT_READ_FORMAT},
       {"barcode", required_argument, 0, OPT_BARCODE}, {"UMI", required_argument, 0, OPT_UMI},
       {"barcode-whitelist", required_argument, 0, OPT_BARCODE_WHITELIST}, {"barcode-translate", required_argument, 0, OPT_BARCODE_TRANSLATE},
@@ -281,6 +285,7 @@ int parse_options(int argc, char *argv[], Options &opt) {
       case OPT_QUANT: opt.quant_path = optarg; break;
       case OPT_QUANT_FORMAT: opt.quant_format = atoi(optarg); break;
       case OPT_PROMOTE: opt.promote = optarg; opt.has_promote = true; break;
+      case OPT_KREPORT: opt.kreport_path = optarg; break;
       case OPT_EXPAND_TAXID: opt.params.output_expanded = 1; break;       // CentrifugerClass.cpp:453-455
       case OPT_BARCODE: opt.bc_files.push_back(optarg); break;             // CentrifugerClass.cpp:457-466
       case OPT_UMI: opt.um_files.push_back(optarg); break;
@@ -338,6 +343,10 @@ int parse_options(int argc, char *argv[], Options &opt) {
   }
   if (opt.has_promote && opt.params.output_expanded) {   // (the reference's centrifuger-promote cannot process the expandedTaxIDs column either)
     print_log("ERROR: --promote cannot be combined with --expand-taxid: promotion does not cover the expanded tax id lists.");
+    return EXIT_FAILURE;
+  }
+  if (!opt.kreport_path.empty() && opt.params.output_expanded) {   // (--expand-taxid has a classify entry of its own, which the report's hook does not cover)
+    print_log("ERROR: --kreport cannot be combined with --expand-taxid: the report is made by the wide classify entries. Run centrifuger-kreport on the output instead.");
     return EXIT_FAILURE;
   }
   if (!opt.quant_path.empty() && (opt.quant_format < 0 || opt.quant_format > 3)) { print_log("ERROR: --quant-format takes 0, 1, 2 or 3."); return EXIT_FAILURE; }
@@ -513,6 +522,8 @@ struct Run {
   std::vector<cfr_barcode *> whitelists;
   cfr_quant *quant = nullptr;
   std::mutex quant_mu;
+  cfr_kreport *kreport = nullptr;      // --kreport: the host handle that takes the devices' bins and writes the report
+  std::mutex kreport_mu;
   size_t total = 0, classified_reads = 0;
 };
 
@@ -988,6 +999,13 @@ struct DeviceWorker {
       const cfr_status s = cfr_quant_add_results(run.quant, b.results.data(), b.matches.data(), b.n);
       if (s != CFR_OK) die_status("cfr_quant_add_results", s);
     }
+    // --kreport: the reads were counted in HBM by the call above; the script's warning lines come from a host scan of the reads that
+    // carry a tax id without a node (none under --promote: the host then holds promoted assignments)
+    if (run.kreport && !opt.has_promote) {
+      std::lock_guard<std::mutex> kl(run.kreport_mu);
+      const cfr_status s = cfr_kreport_scan_warnings(run.kreport, b.results.data(), b.matches.data(), b.n);
+      if (s != CFR_OK) die_status("cfr_kreport_scan_warnings", s);
+    }
   }
 
   void operator()() {
@@ -1155,6 +1173,11 @@ void load_index_and_devices(Run &run) {
     if (opt.dust && !run.host_dust) cfr_device_index_set_dust(d, 1);
     if (opt.merge && !run.host_merge && (st = cfr_device_index_set_merge(d, 1)) != CFR_OK) die_status("cfr_device_index_set_merge", st);
     if (opt.has_promote && (st = cfr_device_index_set_promote(d, opt.promote.c_str())) != CFR_OK) die_status("cfr_device_index_set_promote", st);
+    if (!opt.kreport_path.empty()) {
+      cfr_kreport_options ko;
+      cfr_kreport_options_default(&ko);
+      if ((st = cfr_device_index_set_kreport(d, &ko)) != CFR_OK) die_status("cfr_device_index_set_kreport", st);
+    }
     run.devs.push_back(d);
   }
   run.clk.add(T_DEVICE, t0);
@@ -1166,6 +1189,12 @@ void load_index_and_devices(Run &run) {
     qo.device = opt.gpus[0];
     const cfr_status s = cfr_quant_open(opt.idx.c_str(), &qo, &run.quant);
     if (s != CFR_OK) die_status("cfr_quant_open", s);
+  }
+  if (!opt.kreport_path.empty()) {
+    cfr_kreport_options ko;
+    cfr_kreport_options_default(&ko);
+    const cfr_status s = cfr_kreport_open(opt.idx.c_str(), &ko, -1, &run.kreport);      // (host handle: the roll-up and the writer; the counting is the devices')
+    if (s != CFR_OK) die_status("cfr_kreport_open", s);
   }
 }
 
@@ -1184,6 +1213,26 @@ void load_index_and_devices(Run &run) {
     s = cfr_quant_write(run.quant, opt.quant_format, opt.quant_path.c_str());
     if (s != CFR_OK) die_status("cfr_quant_write", s);
     cfr_quant_destroy(run.quant);
+  }
+  if (run.kreport) {                        // every device's bins summed into the host handle, then the script's report
+    size_t nb = 0;
+    cfr_kreport_bins(run.kreport, &nb);
+    std::vector<uint64_t> own(nb), score(nb);
+    for (auto *d : run.devs) {
+      cfr_status s = cfr_device_index_kreport_counts(d, own.data(), score.data(), nb, nullptr);
+      if (s != CFR_OK) die_status("cfr_device_index_kreport_counts", s);
+      if ((s = cfr_kreport_add_counts(run.kreport, own.data(), score.data(), nb)) != CFR_OK) die_status("cfr_kreport_add_counts", s);
+    }
+    size_t nw = 0;
+    (void)cfr_kreport_warnings(run.kreport, nullptr, 0, &nw);
+    if (opt.has_promote) print_log("--kreport: tax ids without a node are counted at the root; their lines are not counted under --promote.");
+    else if (nw) print_log("--kreport: %lu tax ids without a node were assigned to the root (centrifuger-kreport prints a line for each).", (unsigned long)nw);
+    if (run.total == 0) print_log("--kreport: no reads, no report (centrifuger-kreport: No sequence matches with given settings).");
+    else {
+      const cfr_status s = cfr_kreport_write(run.kreport, opt.kreport_path.c_str());
+      if (s != CFR_OK) die_status("cfr_kreport_write", s);
+    }
+    cfr_kreport_close(run.kreport);
   }
   for (auto *w : run.whitelists) cfr_barcode_destroy(w);
   for (auto *d : run.devs) cfr_device_index_destroy(d);

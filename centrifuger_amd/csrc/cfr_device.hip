@@ -10,9 +10,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <thread>
+#include <stdexcept>
 #include <type_traits>
 
 #include "cfr_hip_util.hpp"
+#include "cfr_kreport.hpp"
 #include "cfr_promote.hpp"
 #include "cfr_tail.hpp"      // dust_mask: the host twin the device SDUST falls back to
 #include "cfr_kernels.hip.inc"
@@ -34,7 +36,7 @@ constexpr size_t kCtlWords = 4;      // words of a sub-batch's control block the
 
 enum Slot : size_t {
   S_CAP = 0, S_HITOFF, S_RAW, S_CHAINCNT, S_SCAN2, S_POOL_E, S_POOL_V, S_POOLCTL, S_POOLCTL1, S_FIN, S_FINCNT, S_FINROWS, S_FINOFF, S_HITS, S_ROWSPER, S_ROWOFF, S_ROWS,
-  S_ROWVALS, S_PACK1, S_PACK2, S_READROWS, S_READROWOFF, S_ENTRIES, S_RESULTS, S_MATCHES, S_RESULTS1, S_MATCHES1, S_SCAN, S_IN_B1, S_IN_O1, S_IN_B2, S_IN_O2, S_DUSTPOOL, S_DUSTPOOL2, S_DUSTTMP, S_DUSTTMP2, S_DUSTFLAG, S_DUSTFLAG2, S_HEAVY, S_HEAVYB, S_HEAVYB1, S_CAP1, S_HITOFF1, S_RAW1, S_CHAINCNT1, S_SCAN1, S_HEAVY1, S_CRES, S_CRES1, S_CMATCH, S_CMATCH1, S_WIDEIDX, S_WIDERES, S_WIDEMATCH, S_WIDECNT, S_PCODES1, S_PCODES2, S_CAPALL, S_HITALL, S_SCANALL, S_P0, S_P1, S_P2, S_P3, S_P4, S_P5, S_EXPPOOL, S_EXPCUR, S_SLOW, S_SLOW1, S_LIST, S_LIST1, S_LISTCTR, S_IN_Q1, S_IN_Q2, S_MRG_B1, S_MRG_B2, S_MRG_Q1, S_MRG_Q2, S_MRG_O1, S_MRG_O2, S_MRG_LEN1, S_MRG_LEN2, S_MRG_DEC, S_MRG_SCAN, S_COUNT
+  S_ROWVALS, S_PACK1, S_PACK2, S_READROWS, S_READROWOFF, S_ENTRIES, S_RESULTS, S_MATCHES, S_RESULTS1, S_MATCHES1, S_SCAN, S_IN_B1, S_IN_O1, S_IN_B2, S_IN_O2, S_DUSTPOOL, S_DUSTPOOL2, S_DUSTTMP, S_DUSTTMP2, S_DUSTFLAG, S_DUSTFLAG2, S_HEAVY, S_HEAVYB, S_HEAVYB1, S_CAP1, S_HITOFF1, S_RAW1, S_CHAINCNT1, S_SCAN1, S_HEAVY1, S_CRES, S_CRES1, S_CMATCH, S_CMATCH1, S_WIDEIDX, S_WIDERES, S_WIDEMATCH, S_WIDECNT, S_PCODES1, S_PCODES2, S_CAPALL, S_HITALL, S_SCANALL, S_P0, S_P1, S_P2, S_P3, S_P4, S_P5, S_EXPPOOL, S_EXPCUR, S_SLOW, S_SLOW1, S_LIST, S_LIST1, S_LISTCTR, S_IN_Q1, S_IN_Q2, S_MRG_B1, S_MRG_B2, S_MRG_Q1, S_MRG_Q2, S_MRG_O1, S_MRG_O2, S_MRG_LEN1, S_MRG_LEN2, S_MRG_DEC, S_MRG_SCAN, S_KRBIN, S_KRSCORE, S_COUNT
 };
 
 }  // namespace
@@ -684,6 +686,7 @@ void DeviceIndex::release() {            // idempotent: also the clean-up of a c
   for (void *p : owned_) (void)hipFree(p);
   owned_.clear();
   promo_table_ = nullptr; promote_on_ = false; promote_tables_ = PromoteTables{};     // (the table was one of owned_)
+  kreport_count_ = kreport_max_ = nullptr; kreport_on_ = false; kreport_tables_ = PromoteTables{};     // (and so were the bins)
   for (void *p : temps_) (void)hipFree(p);
   temps_.clear();
   for (auto &s : slots_) if (s.p) (void)hipFree(s.p);
@@ -693,6 +696,7 @@ void DeviceIndex::release() {            // idempotent: also the clean-up of a c
   auto drop_event = [](hipEvent_t &e) { if (e) (void)hipEventDestroy(e); e = nullptr; };
   for (auto &set : evs_) for (auto &e : set) drop_event(e);
   for (auto &set : promote_ev_) for (auto &e : set) drop_event(e);
+  for (auto &set : kreport_ev_) for (auto &e : set) drop_event(e);
   for (auto &e : tail_done_) drop_event(e);
   for (auto &e : copy_done_) drop_event(e);
   for (auto &e : h2d_done_) drop_event(e);
@@ -1236,6 +1240,38 @@ void DeviceIndex::set_promote(const char *level) {
   promote_on_ = true;
 }
 
+void DeviceIndex::set_kreport(const KreportOptions *opt) {
+  HIP_CHECK(hipSetDevice(device_));
+  if (!opt) { kreport_on_ = false; return; }
+  if (opt->no_lca) throw std::invalid_argument("cfr_device_index_set_kreport: --no-lca adds fractions in file order: it runs on the host, from the TSV");
+  if (view_.node_cnt >= 0xfffffffeull) throw HipError{"the report needs a taxonomy below 2^32 nodes", -2};
+  uint64_t one_node = view_.node_cnt;
+  for (uint64_t i = 0; i < host_->tax.node_cnt; ++i) if (host_->tax.orig_taxid[i] == 1) one_node = i;
+  if (one_node >= view_.node_cnt) throw FormatError{"cfr_device_index_set_kreport: the taxonomy holds no node with tax id 1: the report is the tree below that node"};
+  kreport_tables_ = PromoteTables{view_.tax_parent, view_.tax_orig, view_.seq_to_tax, view_.tax_rank, view_.tax_depth,
+                                  view_.node_cnt, view_.seq_cnt, view_.tax_root, one_node};
+  for (auto &set : kreport_ev_) for (auto &e : set) if (!e) HIP_CHECK(hipEventCreate(&e));
+  const size_t nb = (size_t)view_.node_cnt + 1;
+  if (!kreport_count_) { kreport_count_ = dev_alloc<uint64_t>(nb); kreport_max_ = dev_alloc<uint64_t>(nb); }
+  HIP_CHECK(hipMemsetAsync(kreport_count_, 0, nb * 8, stream_));
+  HIP_CHECK(hipMemsetAsync(kreport_max_, 0, nb * 8, stream_));
+  HIP_CHECK(hipStreamSynchronize(stream_));
+  kreport_opt_ = *opt;
+  kreport_on_ = true;
+}
+
+void DeviceIndex::kreport_counts(uint64_t *own, uint64_t *own_score, double *seq_count) {
+  HIP_CHECK(hipSetDevice(device_));
+  if (!kreport_count_) throw std::invalid_argument("cfr_device_index_kreport_counts: the report was never switched on (cfr_device_index_set_kreport)");
+  const size_t nb = (size_t)view_.node_cnt + 1;
+  HIP_CHECK(hipStreamSynchronize(stream_));
+  std::vector<uint64_t> c(nb);
+  HIP_CHECK(hipMemcpy(c.data(), kreport_count_, nb * 8, hipMemcpyDeviceToHost));
+  if (own) memcpy(own, c.data(), nb * 8);
+  if (own_score) HIP_CHECK(hipMemcpy(own_score, kreport_max_, nb * 8, hipMemcpyDeviceToHost));
+  if (seq_count) { double s = 0; for (uint64_t v : c) s += (double)v; *seq_count = s; }
+}
+
 void DeviceIndex::dust_mask_host(uint8_t *bases, const uint64_t *offs, size_t n) {
   HIP_CHECK(hipSetDevice(device_));
   if (n == 0) return;
@@ -1588,10 +1624,20 @@ void DeviceIndex::classify_device(const uint8_t *d_b1, const uint64_t *d_o1, con
     HIP_CHECK(hipMemsetAsync(wide_side.cnt, 0, 8, stream_));
     HIP_CHECK(hipStreamSynchronize(stream_));              // (the compaction kernels may run on another stream)
   }
+  // --kreport: bin and score of every read of the call, written per sub-batch in copy_out and added into the bins when the call has settled
+  const bool kreport_here = kreport_on_ && !compact;
+  uint32_t *kr_bin = kreport_here ? (uint32_t *)scratch(S_KRBIN, n * 4) : nullptr;
+  uint64_t *kr_score = kreport_here ? (uint64_t *)scratch(S_KRSCORE, n * 8) : nullptr;
   // results / matches of piece k leave through the buffer pair of its parity while piece k+1 computes
   auto copy_out = [&](size_t k, const cfr_result *d_res, const cfr_match *d_match, uint64_t extent, const void *d_flag, unsigned long long *h_flag, hipStream_t st) {
     const size_t lo = pieces[k].first, cnt = pieces[k].second;
     const int par = (int)(k & 1);
+    if (kreport_here) {                     // --kreport: in front of the promotion, so the report sees unpromoted assignments.  A sub-batch that is
+      HIP_CHECK(hipEventRecord(kreport_ev_[k][0], st));      // computed again writes its reads' entries again: the fold counts nothing
+      const unsigned cap = overlap_now_ && tail_blocks_per_cu_ ? (unsigned)(num_cus_ * tail_blocks_per_cu_) : 0u;
+      kreport_launch_fold(kreport_tables_, kreport_opt_, d_res, d_match, cnt, stride * lo, kr_bin + lo, kr_score + lo, st, cap);
+      HIP_CHECK(hipEventRecord(kreport_ev_[k][1], st));
+    }
     if (promote_on_ && !compact) {          // --promote: the sub-batch's results rewritten where they lie, in front of their copy
       HIP_CHECK(hipEventRecord(promote_ev_[k][0], st));
       // (beside the next sub-batch's search it is held to the post stage's few blocks per CU, like the kernels in front of it)
@@ -1833,7 +1879,21 @@ void DeviceIndex::classify_device(const uint8_t *d_b1, const uint64_t *d_o1, con
     if (++exp_attempt_ > 3) { exp_attempt_ = 0; throw HipError{"the pool of --expand-taxid records did not settle in three runs of the batch", -6}; }
     ++last_stats_exp_retries_;
     classify_device(orig_b1, d_o1, orig_b2, d_o2, n, total1, total2, results, matches, match_cap, match_extent, src, compact);
-  } else exp_attempt_ = 0;
+    return;                                 // (the run that settled has counted the reads)
+  }
+  exp_attempt_ = 0;
+  last_kreport_ms = 0.f;
+  if (kreport_here) {                       // every sub-batch has its final results, every stream is idle: count the reads of the call, once
+    HIP_CHECK(hipEventRecord(kreport_ev_[kMaxSub][0], stream_));
+    kreport_launch_accumulate(kr_bin, kr_score, n, kreport_count_, kreport_max_, (uint32_t)view_.node_cnt + 1, stream_);
+    HIP_CHECK(hipEventRecord(kreport_ev_[kMaxSub][1], stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    for (size_t k = 0; k <= kMaxSub; ++k) {
+      if (k < kMaxSub && k >= nsub) continue;
+      float t = 0;
+      if (hipEventElapsedTime(&t, kreport_ev_[k][0], kreport_ev_[k][1]) == hipSuccess) last_kreport_ms += t;
+    }
+  }
 }
 
 void DeviceIndex::classify_host(const uint8_t *b1, const uint64_t *o1, const uint8_t *b2, const uint64_t *o2, size_t n,

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "cfr_index.hpp"
+#include "cfr_kreport_core.hpp"
 #include "cfr_promote_core.hpp"
 
 namespace cfr {
@@ -217,6 +218,17 @@ class DeviceIndex {
   bool promote() const { return promote_on_; }
   float last_promote_ms = 0.f;          // device time of the promotion kernels of the last classify call (0 when switched off)
 
+  // --kreport (centrifuger-kreport inside the run, cfr_kreport.hpp): when switched on, every wide classify call folds the reads of a
+  // sub-batch into bin / score arrays of the call (k_kreport_fold, in front of the promotion launch: the report sees unpromoted
+  // assignments) and, once the call has settled - after the last re-run of a sub-batch or of the whole batch, never in a call that
+  // throws - adds them into the image's persistent bins (k_kreport_accumulate).  opt nullptr: off (the default: nothing is allocated
+  // or launched).  Switching it on zeroes the bins.  no_lca is refused: fractions are added in file order, on the host.
+  void set_kreport(const KreportOptions *opt);
+  bool kreport() const { return kreport_on_; }
+  uint64_t kreport_bins() const { return view_.node_cnt + 1; }
+  void kreport_counts(uint64_t *own, uint64_t *own_score, double *seq_count);     // waits for the stream; node_cnt + 1 entries each
+  float last_kreport_ms = 0.f;          // device time of the report's kernels of the last classify call (0 when switched off)
+
  private:
   struct Merged { const uint8_t *b1; const uint64_t *o1; const uint8_t *b2; const uint64_t *o2; uint64_t t1, t2;
                   const int8_t *q1, *q2; const int32_t *dec; };                  // dec: kind[n], overlap[n], offset[n] on the device
@@ -227,6 +239,10 @@ class DeviceIndex {
   PromoteLevel promote_level_{};
   PromoteTables promote_tables_{};
   uint32_t *promo_table_ = nullptr;      // promo[node] of the level in force (owned_; made on the first rank level)
+  bool kreport_on_ = false;
+  KreportOptions kreport_opt_{};
+  PromoteTables kreport_tables_{};
+  uint64_t *kreport_count_ = nullptr, *kreport_max_ = nullptr;     // the persistent bins (owned_; made when the switch is first turned on)
   hipEvent_t merge_ev_[2] = {};
   void init(const HostIndex &h, const cfr_device_options &opt);
   void release();
@@ -282,6 +298,7 @@ class DeviceIndex {
   hipEvent_t evs_[kMaxSub][9] = {};      // per sub-batch: 0-2 around the search, 8 and 3-7 around the stages behind it
   hipEvent_t *ev_ = nullptr;
   hipEvent_t promote_ev_[kMaxSub][2] = {};   // around the promotion kernel of every sub-batch (made when the switch is first turned on)
+  hipEvent_t kreport_ev_[kMaxSub + 1][2] = {};   // around the fold of every sub-batch, and ([kMaxSub]) around the accumulate of the call
   hipStream_t copy_stream_ = nullptr, h2d_stream_ = nullptr, tail_stream_ = nullptr, dust_stream_ = nullptr;
   hipStream_t search2_stream_ = nullptr, search_stream_ = nullptr;   // the second search stream; the stream launch_search enqueues on (nullptr: stream_)
   hipEvent_t prep_done_ = nullptr;

@@ -465,6 +465,67 @@ cfr_status cfr_promote_close(cfr_promote *h);
 cfr_status cfr_device_index_set_promote(cfr_dev_index *d, const char *level);
 cfr_status cfr_last_promote_ms(const cfr_dev_index *d, float *ms);
 
+/* ---- centrifuger-kreport: the Kraken-style report, reads counted per taxon (the reference's Perl script centrifuger-kreport;
+ * the semantics are stated in csrc/cfr_kreport_core.hpp) ----
+ * Bins: node_cnt + 1 of them, the compact nodes and then "unclassified" (tax id 0).
+ * cfr_kreport_open reads <prefix>.2.cfr only; a taxonomy without a node of tax id 1 is CFR_ERR_FORMAT.  device = -1: the host twin
+ *   alone, no GPU is touched; device >= 0: the kernels of cfr_kreport.hip on that GPU (CFR_ERR_NO_DEVICE without it: no fall-back).
+ * cfr_kreport_add_results: reads as the wide classify entries leave them (host buffers), unpromoted; read i owns
+ *   matches[match_begin, match_begin + n_match).  Not with no_lca (CFR_ERR_ARG): that mode adds fractions in file order.
+ * cfr_kreport_add_tsv: a classification file, plain or gz, "-" = stdin; columns are found by the names in its header line; rows are
+ *   grouped by numMatches as the script does.  no_lca runs on the host, one thread, whatever `device` is.
+ * cfr_kreport_add_count_table: rows of `taxID count` (the script's --is-count-table).  Host only.
+ * cfr_kreport_add_counts: bins downloaded from device images (cfr_device_index_kreport_counts, below) added in; n = node_cnt + 1.
+ * cfr_kreport_counts: own and clade counts, own and clade maximum scores (each node_cnt + 1 entries, any may be NULL) and the
+ *   script's $seq_count; cap = entries every array given can take (CFR_ERR_CAPACITY below node_cnt + 1).
+ * cfr_kreport_warnings: the tax ids of the "Couldn't find parent of taxID ... - directly assigned to root." lines the script
+ *   prints for everything added so far, in its order.  *count = their number; CFR_ERR_CAPACITY when cap is smaller.
+ * cfr_kreport_write: the report; path NULL or "-" = stdout.  Nothing counted: CFR_ERR_ARG with the script's message ("No sequence
+ *   matches with given settings") in cfr_last_error(), and nothing is written. */
+typedef struct cfr_kreport cfr_kreport;
+typedef struct {
+  int32_t has_min_score, has_min_length;   /* whether --min-score / --min-length were given */
+  uint64_t min_score;
+  int64_t min_length;
+  int32_t no_lca, show_zeros, score_data;  /* --no-lca, --show-zeros, --report-score-data */
+  uint32_t max_blocks;                     /* device: at most that many blocks per kernel (the lanes stride); 0 = as many as the reads need */
+  uint32_t lds_slots;                      /* device: slots of the accumulate kernel's LDS table, a power of two in [64, 2048]; 0 = 1024 */
+  int32_t threads;                         /* host twin: threads over the reads; 0 = up to 16 */
+  int32_t pad;
+} cfr_kreport_options;
+typedef struct {
+  float fold_ms;        /* device time of k_kreport_fold of the last cfr_kreport_add_results (host twin: its wall time) */
+  float accumulate_ms;  /* ... of k_kreport_accumulate (host twin: 0) */
+  float parse_ms;       /* wall time of reading and parsing files so far, without the add_results calls inside */
+} cfr_kreport_stats;
+void cfr_kreport_options_default(cfr_kreport_options *o);
+cfr_status cfr_kreport_open(const char *idx_prefix, const cfr_kreport_options *opts, int device, cfr_kreport **out);
+cfr_status cfr_kreport_add_results(cfr_kreport *h, const cfr_result *results, const cfr_match *matches, size_t n);
+cfr_status cfr_kreport_scan_warnings(cfr_kreport *h, const cfr_result *results, const cfr_match *matches, size_t n);   /* the warning lines of these (unpromoted) reads alone, nothing counted: for reads a device image counts */
+cfr_status cfr_kreport_add_tsv(cfr_kreport *h, const char *path);
+cfr_status cfr_kreport_add_count_table(cfr_kreport *h, const char *path);
+cfr_status cfr_kreport_add_counts(cfr_kreport *h, const uint64_t *own, const uint64_t *own_score, size_t n);
+cfr_status cfr_kreport_bins(cfr_kreport *h, size_t *n);
+cfr_status cfr_kreport_counts(cfr_kreport *h, uint64_t *own, uint64_t *clade, uint64_t *own_score, uint64_t *clade_score, size_t cap,
+                              double *seq_count);
+cfr_status cfr_kreport_warnings(cfr_kreport *h, uint64_t *taxids, size_t cap, size_t *count);
+cfr_status cfr_kreport_write(cfr_kreport *h, const char *path);
+cfr_status cfr_kreport_get_stats(cfr_kreport *h, cfr_kreport_stats *st);
+cfr_status cfr_kreport_close(cfr_kreport *h);
+/* cfr_device_index_set_kreport(d, opts): every following call of the wide classify entries (cfr_classify_batch, _resident, _submit /
+ * _wait, _packed, _merged, _resident_merged) counts its reads into node_cnt + 1 bins that stay in the image's HBM: k_kreport_fold runs
+ * per sub-batch behind the tail, in front of a promotion (the report sees unpromoted assignments), into arrays of the call;
+ * k_kreport_accumulate runs once when the call has settled - a sub-batch or a batch that the pipeline computes a second time is
+ * counted once, a call that fails is not counted.  opts NULL switches it off (the default; nothing is allocated or launched then);
+ * switching it on zeroes the bins; no_lca is CFR_ERR_ARG, a taxonomy without tax id 1 CFR_ERR_FORMAT.  Only the filters of opts
+ * matter here.  While it is on, cfr_classify_batch_resident_compact and cfr_classify_batch_expanded return CFR_ERR_ARG.
+ * cfr_device_index_kreport_counts: waits for the image's stream and copies the bins out (own counts, own maximum scores; either may
+ * be NULL; cap = entries each can take, CFR_ERR_CAPACITY below node_cnt + 1) and their sum; feed them to cfr_kreport_add_counts.
+ * cfr_last_kreport_ms: device time of the report's kernels of the last classify call, all sub-batches (0 when switched off). */
+cfr_status cfr_device_index_set_kreport(cfr_dev_index *d, const cfr_kreport_options *opts);
+cfr_status cfr_device_index_kreport_counts(cfr_dev_index *d, uint64_t *own, uint64_t *own_score, size_t cap, double *seq_count);
+cfr_status cfr_last_kreport_ms(const cfr_dev_index *d, float *ms);
+
 /* ---- raw FASTA/FASTQ text -> flat bases + offsets (what ReadFiles.hpp:212-330 and kseq do line by line) ----
  * The tokeniser accepts "regular" text - 4-line FASTQ, FASTA whose sequence lines start with neither '@' nor '+' - and refuses the
  * rest rather than guessing; the grammar is stated in csrc/cfr_tokenize_core.hpp.  What it delivers is a prefix of what the
