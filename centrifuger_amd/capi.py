@@ -108,6 +108,8 @@ EXPORTS = [
     "cfr_kreport_add_counts", "cfr_kreport_bins", "cfr_kreport_counts", "cfr_kreport_warnings", "cfr_kreport_write", "cfr_kreport_get_stats",
     "cfr_kreport_close", "cfr_kreport_scan_warnings", "cfr_device_index_set_kreport", "cfr_device_index_kreport_counts", "cfr_last_kreport_ms",
     "cfr_tokenizer_open", "cfr_tokenize", "cfr_tokenizer_fetch", "cfr_tokenizer_device_reads", "cfr_tokenizer_get_stats", "cfr_tokenizer_close",
+    "cfr_tsv_options_default", "cfr_tsv_open", "cfr_tsv_format", "cfr_tsv_get_stats", "cfr_tsv_close", "cfr_device_index_set_tsv",
+    "cfr_device_index_tsv_last", "cfr_device_index_tsv_last_resident", "cfr_tokenizer_device_records", "cfr_last_tsv_ms",
 ]
 
 _lib = None
@@ -134,7 +136,7 @@ def lib():
                             "cfr_quant_options_default", "cfr_quant_destroy", "cfr_read_format_destroy", "cfr_barcode_destroy",
                             "cfr_barcode_translate_destroy", "cfr_tsv_header_ex", "cfr_format_tsv_ex",
                             "cfr_taxonomy_tax_name", "cfr_taxonomy_seq_name", "cfr_tax_rank_string", "cfr_taxonomy_close",
-                            "cfr_tokenizer_close", "cfr_kreport_options_default"):
+                            "cfr_tokenizer_close", "cfr_kreport_options_default", "cfr_tsv_options_default", "cfr_tsv_close"):
                 getattr(L, name).restype = C.c_int
         for name in ("cfr_quant_destroy", "cfr_read_format_destroy", "cfr_barcode_destroy", "cfr_barcode_translate_destroy"):
             getattr(L, name).restype = None
@@ -150,6 +152,9 @@ def lib():
         L.cfr_format_tsv_ex.restype = C.c_size_t
         L.cfr_tokenizer_close.restype = None
         L.cfr_tokenizer_close.argtypes = [C.c_void_p]
+        L.cfr_tsv_close.restype = None
+        L.cfr_tsv_close.argtypes = [C.c_void_p]
+        L.cfr_tsv_options_default.restype = None
         _lib = L
     return _lib
 
@@ -451,6 +456,35 @@ class DeviceIndex:
         seq = C.c_double(0)
         _check(lib().cfr_device_index_kreport_counts(self._d, _p(own), _p(sc), C.c_size_t(bins), C.byref(seq)))
         return own, sc, seq.value
+
+    def set_tsv(self, on: bool = True):
+        """cfr_device_index_set_tsv: every following wide classify call keeps its final results in HBM for tsv_last()"""
+        _check(lib().cfr_device_index_set_tsv(self._d, C.c_int(int(bool(on)))))
+
+    def _tsv_last(self, call, a, b, cap, want_offsets, n):
+        text = np.zeros(max(cap, 1), dtype=np.uint8)
+        ln = C.c_uint64(0)
+        off = np.zeros(n + 1, dtype=np.uint64) if want_offsets else None
+        status = call(self._d, a, b, _p(text), C.c_uint64(cap), C.byref(ln), _p(off))
+        if status == CFR_ERR_CAPACITY and cap < ln.value:
+            return self._tsv_last(call, a, b, ln.value, want_offsets, n)
+        _check(status)
+        out = text[:ln.value].tobytes()
+        return (out, off) if want_offsets else out
+
+    def tsv_last(self, ids, cap=1 << 16, want_offsets=False):
+        """the rows of the last classify call (set_tsv on) as bytes; ids: the read ids (str or bytes), uploaded by the call"""
+        id_bytes, id_off = pack_ids(ids)
+        return self._tsv_last(lib().cfr_device_index_tsv_last, _p(id_bytes), _p(id_off), cap, want_offsets, len(ids))
+
+    def tsv_last_resident(self, d_text: int, d_records: int, n: int, cap=1 << 16, want_offsets=False):
+        """the same with the ids where Tokenizer.device_records() says they are: nothing but the text crosses PCIe"""
+        return self._tsv_last(lib().cfr_device_index_tsv_last_resident, C.c_void_p(d_text), C.c_void_p(d_records), cap, want_offsets, n)
+
+    def last_tsv_ms(self) -> float:
+        ms = C.c_float(0)
+        _check(lib().cfr_last_tsv_ms(self._d, C.byref(ms)))
+        return ms.value
 
     def last_kreport_ms(self) -> float:
         ms = C.c_float(0)
@@ -1057,6 +1091,12 @@ class Tokenizer:
         _check(lib().cfr_tokenizer_device_reads(self._h, C.byref(b), C.byref(o)))
         return b.value or 0, o.value or 0
 
+    def device_records(self):
+        """-> (d_text, d_records) as ints, for DeviceIndex.tsv_last_resident; valid until the next tokenize() / close()"""
+        t, r = C.c_void_p(), C.c_void_p()
+        _check(lib().cfr_tokenizer_device_records(self._h, C.byref(t), C.byref(r)))
+        return t.value or 0, r.value or 0
+
     @staticmethod
     def ids(text, records):
         t = bytes(text)
@@ -1065,6 +1105,71 @@ class Tokenizer:
     def close(self):
         if self._h:
             lib().cfr_tokenizer_close(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TsvOptions(C.Structure):
+    _fields_ = [("tile_bytes", C.c_int32), ("max_blocks", C.c_int32), ("threads", C.c_int32), ("pad", C.c_int32)]
+
+
+class TsvStats(C.Structure):
+    _fields_ = [("upload_ms", C.c_float), ("len_ms", C.c_float), ("scan_ms", C.c_float), ("write_ms", C.c_float), ("download_ms", C.c_float),
+                ("blocks", C.c_uint64), ("direct_blocks", C.c_uint64)]
+
+
+def pack_ids(ids):
+    """read ids (str or bytes) -> (uint8 bytes back to back, uint64 offsets[n + 1])"""
+    raw = [i.encode("latin-1") if isinstance(i, str) else bytes(i) for i in ids]
+    off = np.zeros(len(raw) + 1, dtype=np.uint64)
+    if raw:
+        off[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
+    return np.frombuffer(b"".join(raw) or b"\0", dtype=np.uint8).copy(), off
+
+
+class Tsv:
+    """cfr_tsv: the rows of a batch as one text, the bytes of Index.format_tsv read after read.  device=None: the host twin."""
+
+    def __init__(self, index: Index, device=None, tile_bytes=0, max_blocks=0, threads=0):
+        self._h = C.c_void_p()
+        self._index = index
+        o = TsvOptions(tile_bytes, max_blocks, threads, 0)
+        _check(lib().cfr_tsv_open(index._h, C.c_int(-1 if device is None else device), C.byref(o), C.byref(self._h)))
+
+    def format_raw(self, results, matches, id_bytes, id_off, cap, n=None, n_slots=None, want_offsets=True):
+        """one cfr_tsv_format call -> (status, len, text uint8[cap], row_offsets or None); raises nothing"""
+        n = len(results) if n is None else n
+        text = np.zeros(max(cap, 1), dtype=np.uint8)
+        ln = C.c_uint64(0)
+        off = np.zeros(n + 1, dtype=np.uint64) if want_offsets else None
+        status = lib().cfr_tsv_format(self._h, _p(results), _p(matches), C.c_size_t(len(matches) if n_slots is None else n_slots), C.c_size_t(n),
+                                      _p(id_bytes), _p(id_off), _p(text), C.c_uint64(cap), C.byref(ln), _p(off))
+        return status, ln.value, text, off
+
+    def format(self, results, matches, ids, cap=1 << 16):
+        """-> (text bytes, row_offsets uint64[n + 1]); grows the buffer when the text needs more than cap"""
+        results = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
+        matches = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        id_bytes, id_off = pack_ids(ids)
+        status, ln, text, off = self.format_raw(results, matches, id_bytes, id_off, cap)
+        if status == CFR_ERR_CAPACITY and ln > cap:
+            status, ln, text, off = self.format_raw(results, matches, id_bytes, id_off, ln)
+        _check(status)
+        return text[:ln].tobytes(), off
+
+    def stats(self) -> TsvStats:
+        st = TsvStats()
+        _check(lib().cfr_tsv_get_stats(self._h, C.byref(st)))
+        return st
+
+    def close(self):
+        if self._h:
+            lib().cfr_tsv_close(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

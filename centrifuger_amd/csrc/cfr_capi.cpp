@@ -22,6 +22,7 @@
 #include "cfr_tail.hpp"
 #include "cfr_threads.hpp"
 #include "cfr_tokenize_core.hpp"
+#include "cfr_tsv.hpp"
 
 struct cfr_index { cfr::HostIndex *h; };
 struct cfr_read_format { cfr::ReadFormat f; };
@@ -36,6 +37,7 @@ struct cfr_taxonomy {
 struct cfr_promote { cfr::Promote *p; };
 struct cfr_kreport { cfr::Kreport *k; };
 struct cfr_tokenizer { cfr::Tokenizer *t; };
+struct cfr_tsv { cfr::Tsv *t; };
 struct cfr_quant { cfr::Quant *q; std::vector<double> weight; int32_t rounds = 0; bool ran = false; };
 // One call at a time per device image: `busy` is held for the length of every entry that touches the image (try_lock:
 // CFR_ERR_BUSY for the second caller) and by the worker thread while it runs a submitted batch.
@@ -98,6 +100,14 @@ std::set<const cfr_tokenizer *> g_tokenizer_live;
 bool tokenizer_live(const cfr_tokenizer *h) {
   std::lock_guard<std::mutex> lk(g_tokenizer_mu);
   return h && g_tokenizer_live.count(h) != 0;
+}
+
+// ... and the cfr_tsv handles
+std::mutex g_tsv_mu;
+std::set<const cfr_tsv *> g_tsv_live;
+bool tsv_live(const cfr_tsv *h) {
+  std::lock_guard<std::mutex> lk(g_tsv_mu);
+  return h && g_tsv_live.count(h) != 0;
 }
 
 // entry guard: the image's buffers, streams and statistics belong to one call at a time
@@ -367,6 +377,7 @@ cfr_status cfr_classify_batch_expanded(cfr_dev_index *d, const uint8_t *bases1, 
   if (!d->d->host().params.output_expanded) return bad_arg("cfr_classify_batch_expanded: the index was opened without cfr_params.output_expanded");
   if (d->d->promote()) return bad_arg("cfr_classify_batch_expanded: promotion is switched on (cfr_device_index_set_promote) and does not cover the expanded lists");
   if (d->d->kreport()) return bad_arg("cfr_classify_batch_expanded: the report is switched on (cfr_device_index_set_kreport) and is made by the wide entries only");
+  if (d->d->tsv()) return bad_arg("cfr_classify_batch_expanded: the rows are made on the device (cfr_device_index_set_tsv), which does not make the expandedTaxIDs column");
   CFR_ENTER(d, "cfr_classify_batch_expanded");
   return guarded([&]() -> cfr_status {
     d->d->classify_host(bases1, offsets1, bases2, offsets2, n, results, matches, match_cap, n_matches);
@@ -475,6 +486,7 @@ cfr_status cfr_classify_batch_resident_compact(cfr_dev_index *d, const void *d_b
   if ((d_bases2 == nullptr) != (d_offsets2 == nullptr)) return bad_arg("cfr_classify_batch_resident_compact: mate buffers must both be given");
   if (d->d->promote()) return bad_arg("cfr_classify_batch_resident_compact: promotion is switched on (cfr_device_index_set_promote) and works on the wide layout: use cfr_classify_batch_resident");
   if (d->d->kreport()) return bad_arg("cfr_classify_batch_resident_compact: the report is switched on (cfr_device_index_set_kreport) and works on the wide layout: use cfr_classify_batch_resident");
+  if (d->d->tsv()) return bad_arg("cfr_classify_batch_resident_compact: the rows are made on the device (cfr_device_index_set_tsv) from the wide layout: use cfr_classify_batch_resident");
   CFR_ENTER(d, "cfr_classify_batch_resident_compact");
   return guarded([&]() -> cfr_status {
     d->d->classify_device((const uint8_t *)d_bases1, (const uint64_t *)d_offsets1, (const uint8_t *)d_bases2,
@@ -1003,6 +1015,97 @@ void cfr_tokenizer_close(cfr_tokenizer *t) {
   }
   delete t->t;
   delete t;
+}
+
+cfr_status cfr_tokenizer_device_records(cfr_tokenizer *t, const void **d_text, const void **d_records) {
+  if (!tokenizer_live(t)) return bad_arg("cfr_tokenizer_device_records: not an open cfr_tokenizer handle");
+  if (!t->t->device_records(d_text, d_records)) return bad_arg("cfr_tokenizer_device_records: the handle is the host twin (opened with device -1)");
+  return CFR_OK;
+}
+
+// ---- the rows of a batch as one text (cfr_tsv_core.hpp) ----
+void cfr_tsv_options_default(cfr_tsv_options *o) { if (o) memset(o, 0, sizeof(*o)); }
+
+cfr_status cfr_tsv_open(const cfr_index *idx, int device, const cfr_tsv_options *o, cfr_tsv **out) {
+  if (!idx || !out) return bad_arg("cfr_tsv_open: null argument");
+  *out = nullptr;
+  if (device < -1) return bad_arg("cfr_tsv_open: device is a HIP ordinal, or -1 for the host twin");
+  cfr_tsv_options opt{};
+  if (o) opt = *o;
+  if (opt.tile_bytes < 0 || opt.max_blocks < 0 || opt.threads < 0) return bad_arg("cfr_tsv_open: an option below 0");
+  return guarded([&]() -> cfr_status {
+    cfr::TsvTables t;
+    t.set_names(idx->h->tax.seq_name);
+    t.rank = idx->h->tax.rank;
+    t.rank.resize((size_t)idx->h->tax.node_cnt);
+    t.set_rank_strings(cfr::tax_rank_string);
+    std::unique_ptr<cfr_tsv> h(new cfr_tsv{nullptr});
+    h->t = device < 0 ? cfr::make_tsv_host(t, opt.threads) : cfr::make_tsv_device(device, t, opt);
+    { std::lock_guard<std::mutex> lk(g_tsv_mu); g_tsv_live.insert(h.get()); }
+    *out = h.release();
+    return CFR_OK;
+  });
+}
+
+cfr_status cfr_tsv_format(cfr_tsv *t, const cfr_result *results, const cfr_match *matches, size_t n_slots, size_t n, const char *id_bytes,
+                          const uint64_t *id_offsets, char *text, uint64_t cap, uint64_t *len, uint64_t *row_offsets) {
+  if (!tsv_live(t)) return bad_arg("cfr_tsv_format: not an open cfr_tsv handle");
+  return guarded([&]() -> cfr_status {
+    if (t->t->format(results, matches, n_slots, n, id_bytes, id_offsets, text, cap, len, row_offsets)) return CFR_OK;
+    g_err = "cfr_tsv_format: the text takes " + std::to_string(*len) + " bytes, the buffer holds " + std::to_string(cap);
+    return CFR_ERR_CAPACITY;
+  });
+}
+
+cfr_status cfr_tsv_get_stats(cfr_tsv *t, cfr_tsv_stats *st) {
+  if (!tsv_live(t)) return bad_arg("cfr_tsv_get_stats: not an open cfr_tsv handle");
+  if (!st) return bad_arg("cfr_tsv_get_stats: null argument");
+  t->t->stats(st);
+  return CFR_OK;
+}
+
+void cfr_tsv_close(cfr_tsv *t) {
+  {
+    std::lock_guard<std::mutex> lk(g_tsv_mu);
+    if (!t || !g_tsv_live.erase(t)) return;
+  }
+  delete t->t;
+  delete t;
+}
+
+cfr_status cfr_device_index_set_tsv(cfr_dev_index *d, int on) {
+  if (!d) return bad_arg("cfr_device_index_set_tsv: null argument");
+  CFR_ENTER(d, "cfr_device_index_set_tsv");
+  return guarded([&]() -> cfr_status { d->d->set_tsv(on != 0); return CFR_OK; });
+}
+
+static cfr_status tsv_last(cfr_dev_index *d, const char *what, const cfr::TsvIds &ids, bool host_ids, char *text, uint64_t cap, uint64_t *len, uint64_t *row_offsets) {
+  if (!d || !len || (!text && cap)) return bad_arg("cfr_device_index_tsv_last: null argument");
+  {
+    std::lock_guard<std::mutex> lk(d->qmu);
+    if (!d->live.empty()) return bad_arg("cfr_device_index_tsv_last: a batch is queued (cfr_classify_batch_submit): wait for it first, the rows are those of the last call");
+  }
+  BusyGuard busy_guard_(d);
+  if (!busy_guard_.ok()) { g_err = std::string(what) + ": this cfr_dev_index is in use by another call (one call at a time per device image)"; return CFR_ERR_BUSY; }
+  return guarded([&]() -> cfr_status {
+    if (d->d->tsv_last(ids, host_ids, text, cap, len, row_offsets)) return CFR_OK;
+    g_err = std::string(what) + ": the text takes " + std::to_string(*len) + " bytes, the buffer holds " + std::to_string(cap);
+    return CFR_ERR_CAPACITY;
+  });
+}
+cfr_status cfr_device_index_tsv_last(cfr_dev_index *d, const char *id_bytes, const uint64_t *id_offsets, char *text, uint64_t cap, uint64_t *len,
+                                     uint64_t *row_offsets) {
+  return tsv_last(d, "cfr_device_index_tsv_last", cfr::TsvIds{id_bytes, id_offsets, nullptr}, true, text, cap, len, row_offsets);
+}
+cfr_status cfr_device_index_tsv_last_resident(cfr_dev_index *d, const void *d_text, const void *d_records, char *text, uint64_t cap, uint64_t *len,
+                                              uint64_t *row_offsets) {
+  return tsv_last(d, "cfr_device_index_tsv_last_resident", cfr::TsvIds{(const char *)d_text, nullptr, (const cfr_read_record *)d_records}, false, text, cap, len,
+                  row_offsets);
+}
+cfr_status cfr_last_tsv_ms(const cfr_dev_index *d, float *ms) {
+  if (!d || !ms) return bad_arg("cfr_last_tsv_ms: null argument");
+  *ms = d->d->last_tsv_ms;
+  return CFR_OK;
 }
 
 // ---- single-cell input: read formats, barcode whitelist, barcode translation ----

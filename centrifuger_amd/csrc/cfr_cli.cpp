@@ -67,10 +67,11 @@ const char *kUsage =
     "\t--gpu-throughput: ... and the 68 GB K-mer table (longest load, fastest kernels) [default: neither, shortest load]\n"
     "\t--parse-threads INT: threads that parse plain single-end read files in pieces [min(-t,8); 1 = sequential reader]\n"
     "\t--gpu-parse: tokenise plain FASTA/FASTQ files (-u, -1/-2) on the GPU that classifies them; the run falls back to the host parsers, with one log line, for what that does not cover [host parsers]\n"
+    "\t--gpu-format: make the TSV rows on the GPU that classified the reads (with --gpu-parse the read ids never leave it); the rows are formatted on the host, with one log line, for what that does not cover [host formatter]\n"
     "\t-h: print this usage message\n"
     "\t-v: print the version information and quit\n";
 
-enum { OPT_UN = 1000, OPT_CL, OPT_NO_DUST, OPT_MIN_HITLEN, OPT_HITK, OPT_SECONDARY, OPT_GPU, OPT_GPU_BATCH, OPT_GPU_THROUGHPUT, OPT_GPU_FASTLOAD, OPT_GPU_BALANCED, OPT_PARSE_THREADS, OPT_GPU_PARSE, OPT_EXPAND_TAXID, OPT_MERGE_READPAIR, OPT_QUANT, OPT_QUANT_FORMAT, OPT_PROMOTE, OPT_KREPORT, OPT_BARCODE, OPT_UMI, OPT_READ_FORMAT, OPT_BARCODE_WHITELIST, OPT_BARCODE_TRANSLATE, OPT_UNSUPPORTED };
+enum { OPT_UN = 1000, OPT_CL, OPT_NO_DUST, OPT_MIN_HITLEN, OPT_HITK, OPT_SECONDARY, OPT_GPU, OPT_GPU_BATCH, OPT_GPU_THROUGHPUT, OPT_GPU_FASTLOAD, OPT_GPU_BALANCED, OPT_PARSE_THREADS, OPT_GPU_PARSE, OPT_GPU_FORMAT, OPT_EXPAND_TAXID, OPT_MERGE_READPAIR, OPT_QUANT, OPT_QUANT_FORMAT, OPT_PROMOTE, OPT_KREPORT, OPT_BARCODE, OPT_UMI, OPT_READ_FORMAT, OPT_BARCODE_WHITELIST, OPT_BARCODE_TRANSLATE, OPT_UNSUPPORTED };
 
 // Persistent workers for the dust and the format stage: a 256 k-read batch is 6 ms of work on 64 threads, less than
 // what starting 64 threads costs, so the threads are started once.
@@ -143,6 +144,7 @@ struct Options {
   int parse_threads = 0;               // 0 = automatic
   bool balanced_profile = false;
   bool gpu_parse = false;              // --gpu-parse: cfr_tokenize on the device instead of SeqReader, where it applies
+  bool gpu_format = false;             // --gpu-format: the rows of a batch made on the device (cfr_device_index_tsv_last), where it applies
   // single-cell input (CentrifugerClass.cpp:374-381)
   std::vector<std::string> bc_files, um_files;
   std::string read_format, whitelist, translate;
@@ -258,7 +260,7 @@ int parse_options(int argc, char *argv[], Options &opt) {
       {"consider-secondary", required_argument, 0, OPT_SECONDARY}, {"gpu", required_argument, 0, OPT_GPU},
       {"gpu-batch", required_argument, 0, OPT_GPU_BATCH}, {"gpu-throughput", no_argument, 0, OPT_GPU_THROUGHPUT},
       {"gpu-fast-load", no_argument, 0, OPT_GPU_FASTLOAD}, {"gpu-balanced", no_argument, 0, OPT_GPU_BALANCED},
-      {"parse-threads", required_argument, 0, OPT_PARSE_THREADS}, {"gpu-parse", no_argument, 0, OPT_GPU_PARSE},
+      {"parse-threads", required_argument, 0, OPT_PARSE_THREADS}, {"gpu-parse", no_argument, 0, OPT_GPU_PARSE}, {"gpu-format", no_argument, 0, OPT_GPU_FORMAT},
       {"sample-sheet", required_argument, 0, OPT_UNSUPPORTED}, {"merge-readpair", no_argument, 0, OPT_MERGE_READPAIR},
       {"quant", required_argument, 0, OPT_QUANT}, {"quant-format", required_argument, 0, OPT_QUANT_FORMAT},
       {"promote", required_argument, 0, OPT_PROMOTE}, {"kreport", required_argument, 0, OPT_KREPORT},
@@ -317,6 +319,7 @@ int parse_options(int argc, char *argv[], Options &opt) {
       case OPT_GPU_BALANCED: opt.balanced_profile = true; break;
       case OPT_PARSE_THREADS: opt.parse_threads = atoi(optarg); break;
       case OPT_GPU_PARSE: opt.gpu_parse = true; break;
+      case OPT_GPU_FORMAT: opt.gpu_format = true; break;
       case OPT_UNSUPPORTED:
         print_log("ERROR: option --%s belongs to a part of Centrifuger outside the MI355X classification path and is not available in this build.",
                   long_options[option_index].name);
@@ -509,6 +512,8 @@ struct Run {
   const std::chrono::steady_clock::time_point t_wall;
   ReadDump un, cl;
   bool gpu_parse = false;              // --gpu-parse, where it applies
+  bool gpu_format = false;             // --gpu-format, where it applies
+  std::atomic<long long> tsv_kernel_ns{0};   // ... and the device time of its kernels (cfr_last_tsv_ms), all batches
   bool protein = false, dumps = false, host_dust = false, host_merge = false, expand = false;
   BatchQueue pending;                  // parsed, waiting for the dust stage
   BatchQueue dusted;                   // masked, waiting for a device
@@ -909,6 +914,9 @@ struct DeviceWorker {
   cfr_tokenizer *tok1 = nullptr, *tok2 = nullptr;       // --gpu-parse: opened with the first raw batch, on this worker's GPU
   cfr_token_info tk1, tk2;
   std::vector<cfr_read_record> recs;
+  std::vector<char> id_bytes;                           // --gpu-format: the batch's ids without their terminators, and their n + 1 offsets
+  std::vector<uint64_t> id_offs;
+  size_t tsv_guess = 1 << 16;                           // ... and the size the text buffer starts with: the largest text so far, and a little
 
   // --gpu-parse: a raw batch on the worker's own tokeniser(s).  true: the reads are in HBM (ids in b.ids); false: the piece is not
   // regular, nothing was taken from it
@@ -923,6 +931,8 @@ struct DeviceWorker {
       ok = !tk2.irregular && tk2.n_records == b.raw_want && tk2.consumed == b.raw2_len;
     }
     if (!ok) return false;
+    b.n = b.raw_want;
+    if (run.gpu_format) return true;               // the ids stay in HBM: the rows are made there (format_on_device), nothing else reads them
     recs.resize(b.raw_want);
     if ((s = cfr_tokenizer_fetch(tok1, recs.data(), nullptr, nullptr)) != CFR_OK) die_status("cfr_tokenizer_fetch", s);
     for (size_t i = 0; i < b.raw_want; ++i) {      // the ids for the TSV: from the record table and the mapped text
@@ -931,7 +941,6 @@ struct DeviceWorker {
       b.ids.insert(b.ids.end(), id, id + recs[i].id_len);
       b.ids.push_back('\0');
     }
-    b.n = b.raw_want;
     return true;
   }
   // ... and the same pieces through SeqReader, as the parallel readers of the host path take them
@@ -1008,6 +1017,42 @@ struct DeviceWorker {
     }
   }
 
+  // --gpu-format: the rows of the batch the device has just classified, as the batch's single TSV part.  The ids come from the
+  // tokeniser's tables in HBM (a resident batch) or go up as bytes.
+  void format_on_device(Batch &b, bool resident) {
+    if (b.tsv_parts.empty()) { b.tsv_parts.resize(1); b.part_hits.resize(1); }
+    std::string &out = b.tsv_parts[0];
+    b.n_parts = 1;
+    b.tsv_device = true;
+    if (!b.n) { out.clear(); return; }
+    const void *d_text = nullptr, *d_rec = nullptr;
+    if (resident) {
+      const cfr_status s = cfr_tokenizer_device_records(tok1, &d_text, &d_rec);
+      if (s != CFR_OK) die_status("cfr_tokenizer_device_records", s);
+    } else {
+      id_bytes.clear(); id_offs.clear();
+      for (size_t i = 0; i < b.n; ++i) {
+        const char *id = b.id(i);
+        id_offs.push_back(id_bytes.size());
+        id_bytes.insert(id_bytes.end(), id, id + strlen(id));
+      }
+      id_offs.push_back(id_bytes.size());
+    }
+    uint64_t len = 0;
+    if (out.size() < tsv_guess) out.resize(tsv_guess);
+    for (;;) {
+      const cfr_status s = resident ? cfr_device_index_tsv_last_resident(dev, d_text, d_rec, &out[0], out.size(), &len, nullptr)
+                                    : cfr_device_index_tsv_last(dev, id_bytes.data(), id_offs.data(), &out[0], out.size(), &len, nullptr);
+      if (s == CFR_ERR_CAPACITY && len > out.size()) { out.resize(len + len / 16); continue; }
+      if (s != CFR_OK) die_status("cfr_device_index_tsv_last", s);
+      break;
+    }
+    tsv_guess = std::max<size_t>(tsv_guess, len + len / 16);
+    out.resize(len);
+    float ms = 0.f;
+    if (cfr_last_tsv_ms(dev, &ms) == CFR_OK) run.tsv_kernel_ns += (long long)((double)ms * 1e6);
+  }
+
   void operator()() {
     while (std::shared_ptr<Batch> b = run.dusted.pop()) {
       auto ts = tick();
@@ -1020,6 +1065,11 @@ struct DeviceWorker {
       if (run.opt.has_barcode && b->n) correct_barcodes(run, dev_no, *b);
       classify(*b, resident);
       run.clk.add(T_CLASSIFY, ts);
+      if (run.gpu_format) {
+        ts = tick();
+        format_on_device(*b, resident);
+        run.clk.add(T_FORMAT, ts);
+      }
       run.classified.push(b);
     }
     cfr_tokenizer_close(tok1);
@@ -1033,6 +1083,14 @@ void format_stage(Run &run, WorkerPool &pool) {
   const Options &opt = run.opt;
   while (std::shared_ptr<Batch> b = run.classified.pop()) {
     const auto ts = tick();
+    if (b->tsv_device) {                     // --gpu-format: the device worker made the rows; what is left is the count of classified reads
+      size_t hits = 0;
+      for (size_t i = 0; i < b->n; ++i) hits += b->results[i].n_match > 0 ? 1 : 0;
+      b->part_hits[0] = hits;
+      run.clk.add(T_FORMAT, ts);
+      run.in_order.mark_done(*b);
+      continue;
+    }
     const int nt = (int)std::min<size_t>((size_t)pool.size(), std::max<size_t>(1, b->n / 4096));
     if (b->tsv_parts.size() < (size_t)nt) { b->tsv_parts.resize((size_t)nt); b->part_hits.resize((size_t)nt); }
     b->n_parts = (size_t)nt;
@@ -1127,6 +1185,15 @@ int plan_run(Run &run) {
     else if (run.protein) why = "a protein index is not covered";
     if (why) { print_log("--gpu-parse is not used, the reads are parsed on the host: %s.", why); run.gpu_parse = false; }
   }
+  // ---- --gpu-format: the same rule
+  run.gpu_format = opt.gpu_format;
+  if (run.gpu_format) {
+    const char *why = nullptr;
+    if (opt.params.output_expanded) why = "the expandedTaxIDs column of --expand-taxid is not made on the device";
+    else if (opt.single_cell) why = "the barcode and UMI columns are not made on the device";
+    else if (opt.params.max_result <= 0) why = "the device keeps -k result slots per read, -k must be positive";
+    if (why) { print_log("--gpu-format is not used, the rows are formatted on the host: %s.", why); run.gpu_format = false; }
+  }
   if (run.protein) opt.dust = false;
   if (run.protein && opt.merge) {
     print_log("ERROR: --merge-readpair is not available with a protein index in this build: a merged pair is searched as one read with an "
@@ -1178,6 +1245,7 @@ void load_index_and_devices(Run &run) {
       cfr_kreport_options_default(&ko);
       if ((st = cfr_device_index_set_kreport(d, &ko)) != CFR_OK) die_status("cfr_device_index_set_kreport", st);
     }
+    if (run.gpu_format && (st = cfr_device_index_set_tsv(d, 1)) != CFR_OK) die_status("cfr_device_index_set_tsv", st);
     run.devs.push_back(d);
   }
   run.clk.add(T_DEVICE, t0);
@@ -1241,6 +1309,7 @@ void load_index_and_devices(Run &run) {
   if (const char *e = getenv("CFR_CLI_TIMING")) if (atoi(e)) {
     static const char *names[] = {"index_open", "device_index", "parse", "dust", "classify", "format", "write", "wall"};
     for (int k = 0; k < 8; ++k) fprintf(stderr, "[timing] %-12s %8.3f s\n", names[k], (double)run.clk.ns[k].load() * 1e-9);
+    if (run.gpu_format) fprintf(stderr, "[timing] %-12s %8.3f s\n", "tsv_kernels", (double)run.tsv_kernel_ns.load() * 1e-9);
   }
   // the TSV must have reached its destination before success is reported (a full disk or a closed pipe otherwise ends in a
   // truncated file with exit status 0); only then is the runtime's teardown skipped (~0.3 s of a sub-second run)

@@ -16,6 +16,7 @@
 #include "cfr_hip_util.hpp"
 #include "cfr_kreport.hpp"
 #include "cfr_promote.hpp"
+#include "cfr_tsv.hpp"
 #include "cfr_tail.hpp"      // dust_mask: the host twin the device SDUST falls back to
 #include "cfr_kernels.hip.inc"
 
@@ -36,7 +37,7 @@ constexpr size_t kCtlWords = 4;      // words of a sub-batch's control block the
 
 enum Slot : size_t {
   S_CAP = 0, S_HITOFF, S_RAW, S_CHAINCNT, S_SCAN2, S_POOL_E, S_POOL_V, S_POOLCTL, S_POOLCTL1, S_FIN, S_FINCNT, S_FINROWS, S_FINOFF, S_HITS, S_ROWSPER, S_ROWOFF, S_ROWS,
-  S_ROWVALS, S_PACK1, S_PACK2, S_READROWS, S_READROWOFF, S_ENTRIES, S_RESULTS, S_MATCHES, S_RESULTS1, S_MATCHES1, S_SCAN, S_IN_B1, S_IN_O1, S_IN_B2, S_IN_O2, S_DUSTPOOL, S_DUSTPOOL2, S_DUSTTMP, S_DUSTTMP2, S_DUSTFLAG, S_DUSTFLAG2, S_HEAVY, S_HEAVYB, S_HEAVYB1, S_CAP1, S_HITOFF1, S_RAW1, S_CHAINCNT1, S_SCAN1, S_HEAVY1, S_CRES, S_CRES1, S_CMATCH, S_CMATCH1, S_WIDEIDX, S_WIDERES, S_WIDEMATCH, S_WIDECNT, S_PCODES1, S_PCODES2, S_CAPALL, S_HITALL, S_SCANALL, S_P0, S_P1, S_P2, S_P3, S_P4, S_P5, S_EXPPOOL, S_EXPCUR, S_SLOW, S_SLOW1, S_LIST, S_LIST1, S_LISTCTR, S_IN_Q1, S_IN_Q2, S_MRG_B1, S_MRG_B2, S_MRG_Q1, S_MRG_Q2, S_MRG_O1, S_MRG_O2, S_MRG_LEN1, S_MRG_LEN2, S_MRG_DEC, S_MRG_SCAN, S_KRBIN, S_KRSCORE, S_COUNT
+  S_ROWVALS, S_PACK1, S_PACK2, S_READROWS, S_READROWOFF, S_ENTRIES, S_RESULTS, S_MATCHES, S_RESULTS1, S_MATCHES1, S_SCAN, S_IN_B1, S_IN_O1, S_IN_B2, S_IN_O2, S_DUSTPOOL, S_DUSTPOOL2, S_DUSTTMP, S_DUSTTMP2, S_DUSTFLAG, S_DUSTFLAG2, S_HEAVY, S_HEAVYB, S_HEAVYB1, S_CAP1, S_HITOFF1, S_RAW1, S_CHAINCNT1, S_SCAN1, S_HEAVY1, S_CRES, S_CRES1, S_CMATCH, S_CMATCH1, S_WIDEIDX, S_WIDERES, S_WIDEMATCH, S_WIDECNT, S_PCODES1, S_PCODES2, S_CAPALL, S_HITALL, S_SCANALL, S_P0, S_P1, S_P2, S_P3, S_P4, S_P5, S_EXPPOOL, S_EXPCUR, S_SLOW, S_SLOW1, S_LIST, S_LIST1, S_LISTCTR, S_IN_Q1, S_IN_Q2, S_MRG_B1, S_MRG_B2, S_MRG_Q1, S_MRG_Q2, S_MRG_O1, S_MRG_O2, S_MRG_LEN1, S_MRG_LEN2, S_MRG_DEC, S_MRG_SCAN, S_KRBIN, S_KRSCORE, S_TSVRES, S_TSVMATCH, S_COUNT
 };
 
 }  // namespace
@@ -683,6 +684,8 @@ DeviceIndex::~DeviceIndex() { release(); }
 void DeviceIndex::release() {            // idempotent: also the clean-up of a constructor that failed half way
   (void)hipSetDevice(device_);
   (void)hipDeviceSynchronize();
+  delete tsv_;                           // (its own stream and buffers)
+  tsv_ = nullptr; tsv_on_ = tsv_valid_ = false;
   for (void *p : owned_) (void)hipFree(p);
   owned_.clear();
   promo_table_ = nullptr; promote_on_ = false; promote_tables_ = PromoteTables{};     // (the table was one of owned_)
@@ -1260,6 +1263,35 @@ void DeviceIndex::set_kreport(const KreportOptions *opt) {
   kreport_on_ = true;
 }
 
+void DeviceIndex::set_tsv(bool on) {
+  HIP_CHECK(hipSetDevice(device_));
+  tsv_valid_ = false;
+  if (!on) { tsv_on_ = false; return; }
+  if (view_.max_result <= 0) throw std::invalid_argument("cfr_device_index_set_tsv: the kept results are laid out by max_result slots per read: max_result > 0");
+  if (!tsv_) {
+    TsvTables t;
+    t.set_names(host_->tax.seq_name);
+    t.rank = host_->tax.rank;
+    t.rank.resize((size_t)host_->tax.node_cnt);
+    t.set_rank_strings(tax_rank_string);
+    cfr_tsv_options o{};
+    tsv_ = make_tsv_device(device_, t, o);
+  }
+  tsv_on_ = true;
+}
+
+bool DeviceIndex::tsv_last(const TsvIds &ids, bool host_ids, char *text, uint64_t cap, uint64_t *len, uint64_t *row_offsets) {
+  HIP_CHECK(hipSetDevice(device_));
+  if (!tsv_on_ || !tsv_valid_ || !tsv_) throw std::invalid_argument("cfr_device_index_tsv_last: the last classify call kept no results (cfr_device_index_set_tsv was off for it)");
+  const cfr_result *d_res = tsv_n_ ? (const cfr_result *)slots_[S_TSVRES].p : nullptr;
+  const cfr_match *d_match = tsv_n_ ? (const cfr_match *)slots_[S_TSVMATCH].p : nullptr;
+  const bool fits = tsv_->format_resident(d_res, d_match, tsv_n_, ids, host_ids, text, cap, len, row_offsets);
+  cfr_tsv_stats st;
+  tsv_->stats(&st);
+  last_tsv_ms = st.len_ms + st.scan_ms + st.write_ms;
+  return fits;
+}
+
 void DeviceIndex::kreport_counts(uint64_t *own, uint64_t *own_score, double *seq_count) {
   HIP_CHECK(hipSetDevice(device_));
   if (!kreport_count_) throw std::invalid_argument("cfr_device_index_kreport_counts: the report was never switched on (cfr_device_index_set_kreport)");
@@ -1423,7 +1455,9 @@ void DeviceIndex::classify_device(const uint8_t *d_b1, const uint64_t *d_o1, con
   pre_hit_off_ = nullptr;
   if (match_extent) *match_extent = 0;
   expanded_raw_.clear();
-  if (n == 0) return;
+  last_tsv_ms = 0.f;
+  tsv_valid_ = false;
+  if (n == 0) { tsv_n_ = 0; tsv_valid_ = tsv_on_ && !compact; return; }
   expand_begin();
   prot_total1_ = total1; prot_total2_ = total2; prot_o1_base_ = d_o1; prot_reads_ = n;
   const uint64_t stride = view_.max_result > 0 ? (uint64_t)view_.max_result : 0;
@@ -1628,6 +1662,10 @@ void DeviceIndex::classify_device(const uint8_t *d_b1, const uint64_t *d_o1, con
   const bool kreport_here = kreport_on_ && !compact;
   uint32_t *kr_bin = kreport_here ? (uint32_t *)scratch(S_KRBIN, n * 4) : nullptr;
   uint64_t *kr_score = kreport_here ? (uint64_t *)scratch(S_KRSCORE, n * 8) : nullptr;
+  // --gpu-format: the final wide results of the call stay in HBM (match_begin counts from the start of the call's matches)
+  const bool tsv_here = tsv_on_ && !compact && stride > 0;
+  cfr_result *tsv_res = tsv_here ? (cfr_result *)scratch(S_TSVRES, n * sizeof(cfr_result)) : nullptr;
+  cfr_match *tsv_match = tsv_here ? (cfr_match *)scratch(S_TSVMATCH, stride * n * sizeof(cfr_match)) : nullptr;
   // results / matches of piece k leave through the buffer pair of its parity while piece k+1 computes
   auto copy_out = [&](size_t k, const cfr_result *d_res, const cfr_match *d_match, uint64_t extent, const void *d_flag, unsigned long long *h_flag, hipStream_t st) {
     const size_t lo = pieces[k].first, cnt = pieces[k].second;
@@ -1644,6 +1682,10 @@ void DeviceIndex::classify_device(const uint8_t *d_b1, const uint64_t *d_o1, con
       const unsigned cap = overlap_now_ && tail_blocks_per_cu_ ? (unsigned)(num_cus_ * tail_blocks_per_cu_) : 0u;
       promote_launch_reads(promote_tables_, promote_level_, promo_table_, const_cast<cfr_result *>(d_res), const_cast<cfr_match *>(d_match), cnt, stride * lo, nullptr, st, cap);
       HIP_CHECK(hipEventRecord(promote_ev_[k][1], st));
+    }
+    if (tsv_here) {                         // --gpu-format: behind the promotion, so the kept rows are the promoted ones
+      HIP_CHECK(hipMemcpyAsync(tsv_res + lo, d_res, cnt * sizeof(cfr_result), hipMemcpyDeviceToDevice, st));
+      if (extent) HIP_CHECK(hipMemcpyAsync(tsv_match + stride * lo, d_match, extent * sizeof(cfr_match), hipMemcpyDeviceToDevice, st));
     }
     if (compact) {                          // the narrow layout is made on the device; what is copied out are its arrays
       cfr_result_compact *c_res = (cfr_result_compact *)scratch(par ? S_CRES1 : S_CRES, std::max(cnt, sb) * sizeof(cfr_result_compact));
@@ -1882,6 +1924,7 @@ void DeviceIndex::classify_device(const uint8_t *d_b1, const uint64_t *d_o1, con
     return;                                 // (the run that settled has counted the reads)
   }
   exp_attempt_ = 0;
+  if (tsv_here) { tsv_n_ = n; tsv_valid_ = true; }     // (every stream that copied a slice has been waited for)
   last_kreport_ms = 0.f;
   if (kreport_here) {                       // every sub-batch has its final results, every stream is idle: count the reads of the call, once
     HIP_CHECK(hipEventRecord(kreport_ev_[kMaxSub][0], stream_));

@@ -38,6 +38,7 @@
 #include "cfr_index.hpp"
 #include "cfr_kreport_core.hpp"
 #include "cfr_promote_core.hpp"
+#include "cfr_tsv_core.hpp"
 
 namespace cfr {
 
@@ -229,7 +230,19 @@ class DeviceIndex {
   void kreport_counts(uint64_t *own, uint64_t *own_score, double *seq_count);     // waits for the stream; node_cnt + 1 entries each
   float last_kreport_ms = 0.f;          // device time of the report's kernels of the last classify call (0 when switched off)
 
+  // --gpu-format (the rows of a call made in HBM, cfr_tsv.hpp): when switched on, every wide classify call keeps its final wide results
+  // in arrays of the call - every sub-batch copied device to device in copy_out, behind the promotion, on the sub-batch's stream; a
+  // sub-batch that is computed again overwrites its slice.  tsv_last formats them: ids by host bytes (host_ids, uploaded by the call) or
+  // by the tokeniser's text and records in HBM.  Off (the default): nothing is allocated or launched.  Needs max_result > 0.
+  void set_tsv(bool on);
+  bool tsv() const { return tsv_on_; }
+  bool tsv_last(const TsvIds &ids, bool host_ids, char *text, uint64_t cap, uint64_t *len, uint64_t *row_offsets);   // false: cap is too small
+  float last_tsv_ms = 0.f;              // device time of the kernels of the last tsv_last since the last classify call (0: none)
+
  private:
+  bool tsv_on_ = false, tsv_valid_ = false;      // tsv_valid_: the kept arrays hold the last classify call's reads
+  size_t tsv_n_ = 0;
+  class Tsv *tsv_ = nullptr;            // the formatter (made when the switch is first turned on)
   struct Merged { const uint8_t *b1; const uint64_t *o1; const uint8_t *b2; const uint64_t *o2; uint64_t t1, t2;
                   const int8_t *q1, *q2; const int32_t *dec; };                  // dec: kind[n], overlap[n], offset[n] on the device
   Merged merge_on_device(const uint8_t *d_b1, const uint64_t *d_o1, const int8_t *d_q1, const uint8_t *d_b2, const uint64_t *d_o2,

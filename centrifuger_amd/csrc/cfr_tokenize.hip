@@ -280,6 +280,12 @@ class TokenizerDevice : public Tokenizer {
     return true;
   }
 
+  bool device_records(const void **d_text, const void **d_records) override {
+    if (d_text) *d_text = text_.get();
+    if (d_records) *d_records = records_.get();
+    return true;
+  }
+
  private:
   void scan(const uint32_t *in, uint32_t *out, size_t count) {
     size_t need = 0;

@@ -155,6 +155,8 @@ class Tokenizer {
   virtual void fetch(cfr_read_record *records, uint64_t *offsets, uint8_t *bases) = 0;
   virtual void stats(cfr_token_stats *st) const { st->copy_in_ms = 0.0; st->kernel_ms = 0.0; }     // (the host twin has one clock: device_ms)
   virtual bool device_reads(const void **d_bases, const void **d_offsets) { (void)d_bases; (void)d_offsets; return false; }
+  // the text and the record table of the last call in HBM (the id of record r: id_len bytes at text + header + 1); false on the host twin
+  virtual bool device_records(const void **d_text, const void **d_records) { (void)d_text; (void)d_records; return false; }
 };
 Tokenizer *make_tokenizer_host();                 // cfr_tokenize_host.cpp
 Tokenizer *make_tokenizer_device(int device);     // cfr_tokenize.hip; throws HipError{.., -1} without that GPU

@@ -565,6 +565,53 @@ typedef struct {
 cfr_status cfr_tokenizer_get_stats(cfr_tokenizer *t, cfr_token_stats *st);
 void cfr_tokenizer_close(cfr_tokenizer *t);
 
+/* ---- the rows of a batch as one text (ResultWriter::Output, ResultWriter.hpp:199-242, for n reads at once; the semantics are stated
+ * in csrc/cfr_tsv_core.hpp) ----
+ * The bytes are those of cfr_format_tsv, read after read: the 8 columns, no header line, no NUL.  The barcode, UMI and expandedTaxIDs
+ * columns are not made here.
+ * cfr_tsv_open: the sequence names and rank codes of idx are copied (device >= 0: uploaded once, the kernels of cfr_tsv.hip run on that
+ *   GPU; CFR_ERR_NO_DEVICE without it: no fall-back).  device = -1: the host twin on `threads` host threads, no GPU is touched.
+ *   options (NULL = defaults; a field of 0 = its default): tile_bytes - a block of 256 reads whose rows take at most that many bytes
+ *   builds them in LDS and streams them out with 16-byte stores, a longer span is written straight to HBM (16 .. 163776);
+ *   max_blocks - at most that many blocks per kernel (the blocks stride).  Both exist for the tests.
+ * cfr_tsv_format: results / matches as the wide classify entries leave them (host arrays): read i owns
+ *   matches[match_begin, match_begin + n_match) when n_match > 0; n_slots = entries of matches.  id i = id_bytes[id_offsets[i],
+ *   id_offsets[i + 1]).  *len = the bytes the text needs; more than cap: CFR_ERR_CAPACITY, *len set, nothing promised about text.
+ *   row_offsets (may be NULL): n + 1 entries, the rows of read i are text[row_offsets[i], row_offsets[i + 1]).
+ *   Checked on the host before anything is launched (CFR_ERR_ARG, cfr_last_error() names the read): null pointers, id_offsets that
+ *   decrease, match_begin + n_match > n_slots.
+ * cfr_tsv_get_stats: device times of the last cfr_tsv_format from events (the host twin: wall times of its two passes in len_ms and
+ *   write_ms); blocks = blocks of 256 reads, direct_blocks = those that took the path straight to HBM.
+ * A handle is used by one thread at a time. */
+typedef struct cfr_tsv cfr_tsv;
+typedef struct { int32_t tile_bytes, max_blocks, threads, pad; } cfr_tsv_options;
+typedef struct { float upload_ms, len_ms, scan_ms, write_ms, download_ms; uint64_t blocks, direct_blocks; } cfr_tsv_stats;
+void cfr_tsv_options_default(cfr_tsv_options *o);
+cfr_status cfr_tsv_open(const cfr_index *idx, int device, const cfr_tsv_options *o, cfr_tsv **out);
+cfr_status cfr_tsv_format(cfr_tsv *t, const cfr_result *results, const cfr_match *matches, size_t n_slots, size_t n,
+                          const char *id_bytes, const uint64_t *id_offsets, char *text, uint64_t cap, uint64_t *len, uint64_t *row_offsets);
+cfr_status cfr_tsv_get_stats(cfr_tsv *t, cfr_tsv_stats *st);
+void cfr_tsv_close(cfr_tsv *t);
+/* cfr_device_index_set_tsv(d, 1): every following call of the wide classify entries (cfr_classify_batch, _resident, _submit / _wait,
+ * _packed, _merged, _resident_merged) keeps its final wide results in HBM, in arrays of the image: every sub-batch is copied device to
+ * device behind its promotion (the rows are the promoted ones under cfr_device_index_set_promote), a sub-batch that is computed again
+ * overwrites its slice; the host copies are delivered as before.  Needs max_result > 0 (CFR_ERR_ARG otherwise).  While it is on,
+ * cfr_classify_batch_resident_compact and cfr_classify_batch_expanded return CFR_ERR_ARG.  Off (the default) nothing is allocated or
+ * launched.
+ * cfr_device_index_tsv_last: the rows of the LAST classify call from the kept arrays, as cfr_tsv_format gives them; ids are host
+ *   bytes, uploaded by the call.  CFR_ERR_ARG if the switch was off for that call or a batch is queued, CFR_ERR_BUSY under the usual guard.
+ * cfr_device_index_tsv_last_resident: the same with the ids where the tokeniser left them: d_text / d_records of
+ *   cfr_tokenizer_device_records (mate 1's tokeniser for pairs) - id of read i = the id_len bytes at d_text + header + 1; no id
+ *   crosses PCIe.  The records must be those of the reads of that call, in order.
+ * cfr_last_tsv_ms: device time of the kernels of the last cfr_device_index_tsv_last* since the last classify call (0 when there was none). */
+cfr_status cfr_device_index_set_tsv(cfr_dev_index *d, int on);
+cfr_status cfr_device_index_tsv_last(cfr_dev_index *d, const char *id_bytes, const uint64_t *id_offsets,
+                                     char *text, uint64_t cap, uint64_t *len, uint64_t *row_offsets);
+cfr_status cfr_device_index_tsv_last_resident(cfr_dev_index *d, const void *d_text, const void *d_records,
+                                              char *text, uint64_t cap, uint64_t *len, uint64_t *row_offsets);
+cfr_status cfr_tokenizer_device_records(cfr_tokenizer *t, const void **d_text, const void **d_records);   /* device handle only; valid until the next cfr_tokenize / close */
+cfr_status cfr_last_tsv_ms(const cfr_dev_index *d, float *ms);
+
 /* ---- single-cell input: read formats, barcode whitelist, barcode translation (ReadFormatter.hpp, BarcodeCorrector.hpp,
  * BarcodeTranslator.hpp; the flow of CentrifugerClass.cpp:163-224, :565-574) ----
  * Handles of their own, independent of any cfr_dev_index; one call at a time per handle.  Barcodes, reads and comments are flat
