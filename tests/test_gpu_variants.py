@@ -87,6 +87,23 @@ def test_parity_suite_under_switches(name):
     assert " passed" in tail
 
 
+WORLD_VARIANTS = ["search_v1", "no_derived_tables", "text_mode_early", "lean_image", "wide_tables_text_mode_early", "no_wide_text_mode",
+                  "wide_text_mode_6_rows_early", "no_team_tail", "post_fast", "post_pool_growth", "run_block_layout"]
+
+
+@pytest.mark.parametrize("name", WORLD_VARIANTS)
+def test_index_worlds_under_switches(name):
+    """Hit lists and TSV rows of tests/test_gpu_worlds.py (shared blocks, both strands, repeats, ragged sequences: ranges of 2 .. 900
+    rows at every hand-over of the search, folds across genera) under the switch sets that change the search, the locate and the fold."""
+    env = dict(os.environ, CFR_DEBUG_ENV="1")
+    env.update(VARIANTS[name])
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_worlds.py"), "-m", "gpu", "-x", "-q", "-k", "hit_lists or tsv"],
+                       env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, cwd=ROOT)
+    tail = r.stdout.decode()[-1500:]
+    assert r.returncode == 0, f"{name} {VARIANTS[name]}:\n{tail}"
+    assert " passed" in tail
+
+
 @pytest.mark.parametrize("name,extra", [("wide_tables", {"CFR_FORCE_WIDE": "1"}), ("no_wide_text_mode", {"CFR_WIDE_ROWS": "0"}),
                                         ("lean_image", {"CFR_FORCE_WIDE": "1", "CFR_FTABX_E8": "1", "CFR_LOC_MEMO_GB": "0"}),
                                         ("no_team_tail", {"CFR_TEAM_TAIL": "0"}), ("team_tail_k1", {"CFR_TEST_K": "1"}), ("team_tail_k5", {"CFR_TEST_K": "5"}),
