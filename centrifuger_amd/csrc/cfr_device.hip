@@ -977,25 +977,30 @@ DeviceIndex::SearchBuf DeviceIndex::launch_search(const uint8_t *d_b1, const uin
         HIP_CHECK(hipMemcpyAsync(h_prof, d_prof, 32 * 8, hipMemcpyDeviceToHost, sst));
         HIP_CHECK(hipMemcpyAsync(h_lc, lc, 3 * 8, hipMemcpyDeviceToHost, sst));
         HIP_CHECK(hipStreamSynchronize(sst));
-        static const char *names[] = {"idle", "table", "table10", "ext", "sa", "text", "text_hits", "lane_iterations", "ext_two_records", "text_rows", "block_loads", "saw", "textw"};
+        static const char *names[] = {"idle", "table", "table10", "ext", "sa", "text", "text_hits", "lane_iterations", "ext_two_records", "text_rows", "block_loads", "saw", "textw", "text_hits_inline"};
         for (int k = 0; k < 2; ++k) {
           fprintf(stderr, "[search prof %s] reads %zu list slots %llu:", k ? "stage 2" : "stage 1", n, h_lc[0]);
-          for (int q = 0; q < 13; ++q) fprintf(stderr, " %s %.2f", names[q], (double)h_prof[16 * k + q] / (double)n);
+          for (int q = 0; q < 14; ++q) fprintf(stderr, q == 6 || q == 13 ? " %s %.4f" : " %s %.2f", names[q], (double)h_prof[16 * k + q] / (double)n);
           fprintf(stderr, " (per read)\n");
         }
       }
     } else
-    if (dbg_env("CFR_SEARCH_PROF") && atoi(dbg_env("CFR_SEARCH_PROF")) && !paired) {
-      // diagnostic: iteration mix of the state machine for this launch, on stderr
+    if (dbg_env("CFR_SEARCH_PROF") && atoi(dbg_env("CFR_SEARCH_PROF"))) {
+      // diagnostic: iteration mix of the state machine for this launch, on stderr (the hits' counts with four decimals: exact for small launches).
+      // Pairs too: four more PROF instantiations (compile time and code object grow by them) so that a test can see from text_hits_inline
+      // that pairs write their text positions into the hit.  Counters: slots 0 .. 13 (14 and 15 of this buffer are the chain counters above).
       unsigned long long *d_prof = (unsigned long long *)scratch(S_P5, 16 * 8), h_prof[16];
-      HIP_CHECK(hipMemsetAsync(d_prof, 0, 15 * 8, sst));
-      if (wide) { if (dyn) CFR_LAUNCH_SEARCH(2, true, true, true, d_prof); else CFR_LAUNCH_SEARCH(2, true, true, false, d_prof); }
+      HIP_CHECK(hipMemsetAsync(d_prof, 0, 14 * 8, sst));
+      if (paired) {
+        if (wide) { if (dyn) CFR_LAUNCH_SEARCH(4, true, true, true, d_prof); else CFR_LAUNCH_SEARCH(4, true, true, false, d_prof); }
+        else { if (dyn) CFR_LAUNCH_SEARCH(4, true, false, true, d_prof); else CFR_LAUNCH_SEARCH(4, true, false, false, d_prof); }
+      } else if (wide) { if (dyn) CFR_LAUNCH_SEARCH(2, true, true, true, d_prof); else CFR_LAUNCH_SEARCH(2, true, true, false, d_prof); }
       else { if (dyn) CFR_LAUNCH_SEARCH(2, true, false, true, d_prof); else CFR_LAUNCH_SEARCH(2, true, false, false, d_prof); }
-      HIP_CHECK(hipMemcpyAsync(h_prof, d_prof, 15 * 8, hipMemcpyDeviceToHost, sst));
+      HIP_CHECK(hipMemcpyAsync(h_prof, d_prof, 14 * 8, hipMemcpyDeviceToHost, sst));
       HIP_CHECK(hipStreamSynchronize(sst));
-      static const char *names[] = {"idle", "table", "table10", "ext", "sa", "text", "text_hits", "lane_iterations", "ext_two_records", "text_rows", "block_loads", "saw", "textw"};
+      static const char *names[] = {"idle", "table", "table10", "ext", "sa", "text", "text_hits", "lane_iterations", "ext_two_records", "text_rows", "block_loads", "saw", "textw", "text_hits_inline"};
       fprintf(stderr, "[search prof] reads %zu lanes %u:", n, blocks * kBlock);
-      for (int q = 0; q < 13; ++q) fprintf(stderr, " %s %.2f", names[q], (double)h_prof[q] / (double)n);
+      for (int q = 0; q < 14; ++q) fprintf(stderr, q == 6 || q == 13 ? " %s %.4f" : " %s %.2f", names[q], (double)h_prof[q] / (double)n);
       fprintf(stderr, " (per read)\n");
     } else if (wide) {
       if (paired) { if (dyn) CFR_LAUNCH_SEARCH(4, false, true, true, nullptr); else CFR_LAUNCH_SEARCH(4, false, true, false, nullptr); }
@@ -1853,6 +1858,8 @@ void DeviceIndex::classify_device(const uint8_t *d_b1, const uint64_t *d_o1, con
     }
   }
   const bool repeated = one_launch && !todo.empty();
+  if (repeated && dbg_env("CFR_POST_STATS"))             // diagnostics: the fallback below really ran (tests/test_gpu_text_pos_in_hit.py)
+    fprintf(stderr, "[cfr] scratch pool ran dry in %zu of %zu sub-batches: repeated in the multi-kernel form\n", todo.size(), nsub);
 
   // ---- multi-kernel form: search, adjust/select, (compact, rows, locate,) tail; one or two 8-byte host syncs per piece
   if (pack_rest_pending) { HIP_CHECK(hipStreamWaitEvent(stream_, copied_[0], 0)); pack_rest_pending = false; }

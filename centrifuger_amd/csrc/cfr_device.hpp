@@ -18,7 +18,9 @@
 //              is then extended by comparing the read with the text 48 bases per step (the rows' suffix positions move in
 //              lock step), instead of one LF step per base.  A hit found that way is kept in TEXT-POSITION space: its rows
 //              are "virtual rows" (the range the search had when it moved to the text, which of its rows survived, and how
-//              many characters were matched since: virt_text_pos), so no inverse suffix array exists anywhere.
+//              many characters were matched since: virt_text_pos), so no inverse suffix array exists anywhere.  A hit that ends
+//              with one row (or two rows of 32 bits) carries the rows' text positions themselves (kVirtInline), which the search
+//              holds in registers when it ends: the post stage then fetches no suffix-array entry for it.
 //   steps    : DERIVED at load time: what FMIndex::BackwardToSampledSA returns, as a step function of the TEXT POSITION of
 //              the row it starts from (breakpoints: position 0 and the selectedSA positions; the premise is verified on
 //              every sampled row, k_memo_check).  locate(row) = steps(SA[row]); locate(virtual row) = steps(SA[entry row] - matched).
@@ -72,7 +74,8 @@ struct ProtView {
   char list[32];             // code -> character
 };
 
-// rows >= kVirtRow are virtual: rows of a hit that was finished on the text (layout: virt_text_pos in cfr_kernels.hip.inc)
+// rows >= kVirtRow are virtual: rows of a hit that was finished on the text (the two layouts - entry range + mask of surviving rows,
+// or the rows' text positions inline (kVirtInline, bit 62) - are described at virt_text_pos in cfr_kernels.hip.inc)
 constexpr uint64_t kVirtRow = 1ull << 63;
 
 // BackwardToSampledSA as a step function of the text position (see cfr_kernels.hip.inc, steps_value)

@@ -19,11 +19,14 @@ namespace cfr {
 
 constexpr uint64_t kSelFlag = 1ull << 63;
 // text-space hits (virt_text_pos below): sp = kVirtRow | delta << kVirtDeltaShift | first row of the entry range (< 2^36).
-// delta has 27 bits (bits 36..62): a search only moves to the text when what is left of it cannot exceed that (kVirtDeltaMax
-// characters; longer exact matches - contigs of > 134 Mbp - stay on the BWT, where the reference's own loop has no limit either).
+// delta has 26 bits (bits 36..61): a search only moves to the text when what is left of it cannot exceed that (kVirtDeltaMax
+// characters; longer exact matches - contigs of > 67 Mbp - stay on the BWT, where the reference's own loop has no limit either).
+// With kVirtInline (bit 62) the hit carries its rows' text positions itself, in place of the first row and of the mask: the one
+// or two rows a search of k_search_chains_v2 ended with, which it holds in registers at that point (virt_text_pos below).
 constexpr uint32_t kVirtDeltaShift = 36;
 constexpr uint64_t kVirtRowMask = (1ull << kVirtDeltaShift) - 1ull;
-constexpr uint32_t kVirtDeltaMax = (1u << 27) - 1u;
+constexpr uint32_t kVirtDeltaMax = (1u << 26) - 1u;
+constexpr uint64_t kVirtInline = 1ull << 62;
 
 // 16-byte gather from an address that is only guaranteed 4-byte alignment (offset arrays, u32 tables, the second half of a
 // 2-bit text pair): one global_load_dwordx4 on gfx950, and well defined because the type says what the alignment is.
@@ -582,7 +585,7 @@ __device__ __forceinline__ uint32_t prot_search_full(const DevView &v, const Cod
   const bool text_ok = v.text8 != nullptr && v.sa32 != nullptr && v.steps.pos != nullptr;
   bool no_text = false;                                    // set when a single row at text position 0 went back to the BWT
   while (l < m) {
-    if (text_ok && !no_text && l >= v.text_min_l && m - l <= (1u << 27) - 1u && ep - sp < 4 && !(sp == ep && sp == v.first_isa)) {   // (m - l: kVirtDeltaMax, virt_text_pos)
+    if (text_ok && !no_text && l >= v.text_min_l && m - l <= kVirtDeltaMax && ep - sp < 4 && !(sp == ep && sp == v.first_isa)) {   // (m - l: kVirtDeltaMax, virt_text_pos)
       // ---- text mode
       uint32_t R = (uint32_t)(ep - sp) + 1u, mask = (1u << R) - 1u;
       uint32_t tp[4], idx[4] = {0, 1, 2, 3};
@@ -734,7 +737,12 @@ __device__ __forceinline__ uint64_t steps_value(const StepView &S, uint64_t p) {
 // so that everything downstream keeps reading ep - sp + 1 as the number of rows and sp == ep as "unique hit".  The rows LF would
 // have led to are ISA[SA[sp0 + k] - delta] (same order: rows with equal BWT symbol keep their order under LF), and
 // BackwardToSampledSA of such a row only depends on its text position SA[sp0 + k] - delta: no inverse suffix array is needed.
+// With kVirtInline in sp the search wrote those text positions themselves (it held them in registers when it ended), and no
+// suffix-array entry is fetched: bits 0..35 of sp = position of the first surviving row, pad = position of the second one (a
+// two-row hit is only written this way where positions have 32 bits); delta is still there, nobody reads it.  One list can hold
+// both forms: hits of 3 or more rows, two-row hits of a 36-bit image and the lookup stage of the two-launch search write the mask.
 __device__ __forceinline__ uint64_t virt_text_pos(const DevView &v, const cfr_hit &H, uint64_t row) {
+  if (H.sp & kVirtInline) return row == H.sp ? (H.sp & kVirtRowMask) : (uint64_t)(uint32_t)H.pad;
   uint32_t m = (uint32_t)H.pad;
   for (uint32_t q = (uint32_t)(row - H.sp); q; --q) m &= m - 1u;               // the (row - sp)-th surviving row
   const uint32_t k = (uint32_t)__ffs((int)m) - 1u;
@@ -1349,7 +1357,7 @@ __global__ __launch_bounds__(256, MINB) void k_search_prot_sm(DevView v, const u
     }
     if (st == PS_DECIDE) {                                     // the head of prot_search_full's loop
       if (l >= m) st = PS_END;
-      else if (text_ok && !no_text && l >= v.text_min_l && m - l <= (1u << 27) - 1u && ep - sp < 4 && !(sp == ep && sp == v.first_isa)) st = PS_SA;
+      else if (text_ok && !no_text && l >= v.text_min_l && m - l <= kVirtDeltaMax && ep - sp < 4 && !(sp == ep && sp == v.first_isa)) st = PS_SA;
       else if (!win_ok(s0 + l, 1u)) { wreq = (s0 + l) & ~3u; ret = PS_DECIDE; st = PS_CODES; }
       else {
         ce = code_at(s0 + l);
@@ -4147,11 +4155,18 @@ __global__ __launch_bounds__(256, STAGE == 1 && !WIDE && CPR == 2 ? CFR_FIRST_MI
     }
   };
 
-  // a search that ended on the text: the hit keeps the range it entered the text with, and which of its rows survived
+  // a search that ended on the text: the hit keeps the range it entered the text with, and which of its rows survived - or, where
+  // the record has room for them, the survivors' text positions themselves (kVirtInline: one row, or two rows of 32 bits; the
+  // four-row form is the only caller with rows <= 4, and tp0 / tp1 are its survivors in row order).  The post stage then needs
+  // no suffix-array entry for the hit.  The lookup stage of the two-launch search keeps the mask (12 bytes of scratch otherwise).
   auto emit_text_hit = [&](uint32_t rows, uint32_t mask) {
     if ((int32_t)l >= v.min_hit_len) {                    // (GetHitsFromRead keeps the hit, Classifier.hpp:283-290; rows >= 1 so sp <= ep)
       cfr_hit h;
-      h.sp = kVirtRow | ((uint64_t)(l - l0) << kVirtDeltaShift) | sp; h.ep = h.sp + (rows - 1u); h.l = (int32_t)l; h.strand = 0; h.offset = (int32_t)t0; h.pad = (int32_t)mask;
+      const bool inl = !FIRST && (rows == 1u || (!WIDE && rows == 2u));
+      h.sp = kVirtRow | ((uint64_t)(l - l0) << kVirtDeltaShift) | (inl ? kVirtInline | (uint64_t)tp0 : sp);
+      h.ep = h.sp + (rows - 1u); h.l = (int32_t)l; h.strand = 0; h.offset = (int32_t)t0;
+      h.pad = (int32_t)(!FIRST && !WIDE && rows == 2u ? (uint32_t)tp1 : mask);
+      if (PROF && inl) ++pc[9];
       out[cnt++] = h;
     }
     in_bs = false;
@@ -4667,6 +4682,7 @@ __global__ __launch_bounds__(256, STAGE == 1 && !WIDE && CPR == 2 ? CFR_FIRST_MI
     atomicAdd(prof + 8, (unsigned long long)p_ext2);
     atomicAdd(prof + 9, (unsigned long long)p_text_rows);
     atomicAdd(prof + 10, (unsigned long long)p_blk);
+    atomicAdd(prof + 13, (unsigned long long)pc[9]);      // text hits that carry their positions (kVirtInline)
   }
 }
 
