@@ -136,3 +136,38 @@ def test_protein_suite_under_switches(name, extra):
     tail = r.stdout.decode()[-1500:]
     assert r.returncode == 0, f"{name}:\n{tail}"
     assert " passed" in tail
+
+
+PROTEIN_WORLD_VARIANTS = {
+    # the hand-out of k_search_prot_sm: one block per CU (every lane takes several chains), chain + stride instead of wave tiles
+    "one_block_per_cu": {"CFR_PROT_BLOCKS": "1"},
+    "static_hand_out": {"CFR_PROT_DYN": "0"},
+    "static_hand_out_one_block_per_cu": {"CFR_PROT_DYN": "0", "CFR_PROT_BLOCKS": "1"},
+    # one chain per lane from start to end (k_search_prot), at 80 registers; the state machine at 6 blocks per CU
+    "chain_per_lane": {"CFR_PROT_SM": "0"},
+    "chain_per_lane_minb_6": {"CFR_PROT_SM": "0", "CFR_PROT_MINB": "6"},
+    "state_machine_minb_6": {"CFR_PROT_SM_MINB": "6"},
+    "tiny_subbatches": {"CFR_SUBBATCH": "37", "CFR_TAPER_FLOOR": "0"},
+    "no_text_mode": {"CFR_TEXT_MODE": "0"},
+    "text_mode_early": {"CFR_TEXT_MIN_L": "3"},
+    "no_kmer_table": {"CFR_FTABX_WIDTH": "0"},
+    "kmer_table_3": {"CFR_FTABX_WIDTH": "3"},
+    "kmer_table_7": {"CFR_FTABX_WIDTH": "7"},
+    "two_arrays": {"CFR_PROT_TWO_ARRAYS": "1"},
+}
+
+
+@pytest.mark.parametrize("name", sorted(PROTEIN_WORLD_VARIANTS))
+@pytest.mark.parametrize("suite", ["worlds", "chains"])
+def test_protein_worlds_and_chains_under_switches(suite, name):
+    """tests/test_gpu_protein_worlds.py (hit lists and TSV rows of every world) and tests/test_gpu_protein_chains.py (more chains than
+    lanes; its own child processes left out) under the switches of the protein search: hand-out, kernel, register budget, sub-batches,
+    text mode, K-mer table width, image form."""
+    env = dict(os.environ, CFR_DEBUG_ENV="1")
+    env.update(PROTEIN_WORLD_VARIANTS[name])
+    file, select = (("test_gpu_protein_worlds.py", "hit_lists or tsv") if suite == "worlds" else ("test_gpu_protein_chains.py", "not child_process"))
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", file), "-m", "gpu", "-x", "-q", "-k", select],
+                       env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, cwd=ROOT, timeout=900)
+    tail = r.stdout.decode()[-1500:]
+    assert r.returncode == 0, f"{name} {PROTEIN_WORLD_VARIANTS[name]}:\n{tail}"
+    assert " passed" in tail
