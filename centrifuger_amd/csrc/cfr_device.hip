@@ -937,7 +937,8 @@ DeviceIndex::SearchBuf DeviceIndex::launch_search(const uint8_t *d_b1, const uin
     // ones whose search reaches a range of 5 .. wide_rows rows over through a list; the full state machine runs over that list
     static const int split_env = dbg_env("CFR_SEARCH_SPLIT") ? atoi(dbg_env("CFR_SEARCH_SPLIT")) : -1;
     const bool prof_run = dbg_env("CFR_SEARCH_PROF") && atoi(dbg_env("CFR_SEARCH_PROF")) && !paired;
-    bool split = sv.sa != nullptr && sv.wide_rows > 4 && nchains < 0xfff00000ull;
+    bool split = sv.sa != nullptr && sv.wide_rows > 4 && nchains < 0xfff00000ull &&
+                 16 * std::max<uint64_t>(nblk1_, nb2) / (uint64_t)(sv.min_hit_len + 1) <= kListCntMax;   // (a record's hit count: kListHitBits)
     if (split_env >= 0) split = split && split_env != 0; else split = split && search_split_default_;
     if (split) {
       uint64_t *list = (uint64_t *)scratch(par ? S_LIST1 : S_LIST, (nchains + ((size_t)num_cus_ * 8 * 4 + 1) * kListChunk) * 32);

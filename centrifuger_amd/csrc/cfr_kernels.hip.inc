@@ -4064,12 +4064,16 @@ constexpr uint32_t kWideRows = 24, kWideRowsWide = 24;
 // in nearly every wave iteration although 8 % of the lane iterations need it):
 // STAGE 1: the state machine WITHOUT wide text mode (no LDS, fewer registers).  A search that reaches a range of 5 .. wide_rows rows is not
 //       continued here: the chain is handed over AT THE START OF THAT SEARCH through a list of 32-byte records {byte that search starts at,
-//       len | t0 << 32, index of its hit list | hits so far << 48, chain}.  Slots are drawn a chunk of kListChunk at a time with one
+//       len | t0 << 32, index of its hit list | hits so far << kListHitBits, chain}.  Slots are drawn a chunk of kListChunk at a time with one
 //       atomic per wave and chunk (one returning atomic per wave ITERATION on one address costs 11 ns each: 3 M per step, profiles/
 //       r6b_ab_lookup_stage.txt); what a wave leaves of a chunk is filled with hole records (chain = ~0).
 // STAGE 2: the full state machine over that list: a record is the chain's parameters (the two P slots), the first search starts at the
 //       record's t0 behind the hits the first stage wrote.  raw / chain_cnt are indexed by chain, so the order of the list does not matter.
 constexpr uint32_t kListChunk = 64;
+// A record's third word: the index of the chain's hit list in `raw` (36 bits: 2 TB of 32-byte hits) and the hits the first stage wrote
+// (28 bits).  A chain is handed over with at most len / (min_hit_len + 1) hits; the host takes the two-launch form only where that stays
+// below kListCntMax for every read of the batch (`split`, where cfr_device.hip launches the search), so the kernel does not look at the count.
+constexpr uint32_t kListHitBits = 36, kListCntMax = (1u << (64 - kListHitBits)) - 1u;
 template <int CPR, bool PROF = false, bool WIDE = false, bool DYN = false, int STAGE = 0>
 #ifndef CFR_FIRST_MIN_BLOCKS
 #define CFR_FIRST_MIN_BLOCKS 5
@@ -4180,7 +4184,7 @@ __global__ __launch_bounds__(256, STAGE == 1 && !WIDE && CPR == 2 ? CFR_FIRST_MI
     uint32_t pending_consume = 0;         // characters of an ended search that are still in the queue
     bool push = false;                    // FIRST: this lane hands its chain over in this iteration
     if (params_pending) {
-      if (LIST) { nx_o1a = P1.x; nx_o1b = P1.y; nx_hoff = P3.x; nx_o2a = P3.y; }      // a record: first byte, len | t0 << 32, hit list | hits << 48, chain
+      if (LIST) { nx_o1a = P1.x; nx_o1b = P1.y; nx_hoff = P3.x; nx_o2a = P3.y; }      // a record: first byte, len | t0 << 32, hit list | hits << kListHitBits, chain
       else {
         nx_o1a = P1.x; nx_o1b = P1.y; nx_hoff = P2;
         if (CPR == 4) { nx_o2a = P3.x; nx_o2b = P3.y; }
@@ -4514,7 +4518,7 @@ __global__ __launch_bounds__(256, STAGE == 1 && !WIDE && CPR == 2 ? CFR_FIRST_MI
           const uint64_t a_start = rc ? (uint64_t)(16 * blk_next - (int64_t)q_n - (int64_t)l) : (uint64_t)(16 * (blk_next + 1) + (int64_t)q_n - 1 + (int64_t)l);
           uint64_t *rec = list + 4ull * (lc_base + lc_used + (uint32_t)__popcll(pm & ((1ull << lane) - 1ull)));
           *reinterpret_cast<ulonglong2 *>(rec) = make_ulonglong2(a_start, (uint64_t)len | ((uint64_t)t0 << 32));
-          *reinterpret_cast<ulonglong2 *>(rec + 2) = make_ulonglong2((uint64_t)(out - raw) | ((uint64_t)cnt << 48), chain);
+          *reinterpret_cast<ulonglong2 *>(rec + 2) = make_ulonglong2((uint64_t)(out - raw) | ((uint64_t)cnt << kListHitBits), chain);
           have_chain = false; in_bs = false;
         }
         lc_used += k;
@@ -4600,7 +4604,7 @@ __global__ __launch_bounds__(256, STAGE == 1 && !WIDE && CPR == 2 ? CFR_FIRST_MI
       cnt = 0; t0 = 0; l = 0; m = 0; in_bs = false; tmode = false; need_end = false; wmode = false; wload = false;
       if (LIST) {                         // the record says it all (the buffer follows the mate)
         len = (uint32_t)nx_o1b; t0 = (uint32_t)(nx_o1b >> 32);
-        out = raw + (nx_hoff & 0xffffffffffffull); cnt = (uint32_t)(nx_hoff >> 48);
+        out = raw + (nx_hoff & ((1ull << kListHitBits) - 1ull)); cnt = (uint32_t)(nx_hoff >> kListHitBits);
       }
       if (DYN) {
         if (dyn_chunk >= 64u) chain_next = tile_chain;

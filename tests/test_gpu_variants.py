@@ -104,6 +104,28 @@ def test_index_worlds_under_switches(name):
     assert " passed" in tail
 
 
+# the small set (with its pair of 4 095 hits in one mate) and the single reads of 4 094 | 4 095 | 4 096 hits under the switches of the search; every read, those of 65 535 .. 70 000 hits and
+# of 2^20 bases included, under the switches of the post stage and under the two-launch search (whose hand-over record counts a chain's hits)
+READ_WORLD_VARIANTS = [(n, "small") for n in ("no_derived_tables", "text_mode_early", "ftabx_8_byte_entries", "ftabx_k17", "wide_tables_text_mode_early",
+                                              "no_wide_text_mode", "wide_text_mode_6_rows_early", "search_v1", "search_static_hand_out",
+                                              "tiny_subbatches_sparse_memo", "run_block_layout")]
+READ_WORLD_VARIANTS += [(n, "all") for n in ("no_team_tail", "post_fast", "post_pool_growth", "two_kernel_post_stage", "search_split_many_subbatches_wave_tiles")]
+
+
+@pytest.mark.parametrize("name,reads", READ_WORLD_VARIANTS)
+def test_read_worlds_under_switches(name, reads):
+    """Hit lists and TSV rows of tests/test_gpu_read_worlds.py (every read length, buffer alignment, non-symbol and mismatch position,
+    chimeras, long reads, reads of many hits, ragged pairs) under the switch sets that change the search and the post stage."""
+    env = dict(os.environ, CFR_DEBUG_ENV="1")
+    env.update(VARIANTS[name])
+    select = "(hit_lists or tsv) and (small or giant_4095)" if reads == "small" else "hit_lists or tsv"
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_read_worlds.py"), "-m", "gpu", "-x", "-q", "-k", select],
+                       env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, cwd=ROOT)
+    tail = r.stdout.decode()[-1500:]
+    assert r.returncode == 0, f"{name} {VARIANTS[name]}:\n{tail}"
+    assert " passed" in tail
+
+
 @pytest.mark.parametrize("name,extra", [("wide_tables", {"CFR_FORCE_WIDE": "1"}), ("no_wide_text_mode", {"CFR_WIDE_ROWS": "0"}),
                                         ("lean_image", {"CFR_FORCE_WIDE": "1", "CFR_FTABX_E8": "1", "CFR_LOC_MEMO_GB": "0"}),
                                         ("no_team_tail", {"CFR_TEAM_TAIL": "0"}), ("team_tail_k1", {"CFR_TEST_K": "1"}), ("team_tail_k5", {"CFR_TEST_K": "5"}),
