@@ -110,6 +110,7 @@ EXPORTS = [
     "cfr_tokenizer_open", "cfr_tokenize", "cfr_tokenizer_fetch", "cfr_tokenizer_device_reads", "cfr_tokenizer_get_stats", "cfr_tokenizer_close",
     "cfr_tsv_options_default", "cfr_tsv_open", "cfr_tsv_format", "cfr_tsv_get_stats", "cfr_tsv_close", "cfr_device_index_set_tsv",
     "cfr_device_index_tsv_last", "cfr_device_index_tsv_last_resident", "cfr_tokenizer_device_records", "cfr_last_tsv_ms",
+    "cfr_gz_options_default", "cfr_gz_open", "cfr_gz_compress", "cfr_gz_dump", "cfr_gz_eof", "cfr_gz_get_stats", "cfr_gz_close",
 ]
 
 _lib = None
@@ -136,7 +137,8 @@ def lib():
                             "cfr_quant_options_default", "cfr_quant_destroy", "cfr_read_format_destroy", "cfr_barcode_destroy",
                             "cfr_barcode_translate_destroy", "cfr_tsv_header_ex", "cfr_format_tsv_ex",
                             "cfr_taxonomy_tax_name", "cfr_taxonomy_seq_name", "cfr_tax_rank_string", "cfr_taxonomy_close",
-                            "cfr_tokenizer_close", "cfr_kreport_options_default", "cfr_tsv_options_default", "cfr_tsv_close"):
+                            "cfr_tokenizer_close", "cfr_kreport_options_default", "cfr_tsv_options_default", "cfr_tsv_close",
+                            "cfr_gz_options_default", "cfr_gz_eof", "cfr_gz_close"):
                 getattr(L, name).restype = C.c_int
         for name in ("cfr_quant_destroy", "cfr_read_format_destroy", "cfr_barcode_destroy", "cfr_barcode_translate_destroy"):
             getattr(L, name).restype = None
@@ -155,6 +157,10 @@ def lib():
         L.cfr_tsv_close.restype = None
         L.cfr_tsv_close.argtypes = [C.c_void_p]
         L.cfr_tsv_options_default.restype = None
+        L.cfr_gz_close.restype = None
+        L.cfr_gz_close.argtypes = [C.c_void_p]
+        L.cfr_gz_options_default.restype = None
+        L.cfr_gz_eof.restype = None
         _lib = L
     return _lib
 
@@ -1170,6 +1176,96 @@ class Tsv:
     def close(self):
         if self._h:
             lib().cfr_tsv_close(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class GzOptions(C.Structure):
+    _fields_ = [("block_bytes", C.c_int32), ("max_blocks", C.c_int32), ("threads", C.c_int32), ("pad", C.c_int32)]
+
+
+class GzStats(C.Structure):
+    _fields_ = [("upload_ms", C.c_float), ("format_ms", C.c_float), ("deflate_ms", C.c_float), ("pack_ms", C.c_float), ("download_ms", C.c_float),
+                ("pad", C.c_uint32), ("blocks", C.c_uint64), ("stored_blocks", C.c_uint64), ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64)]
+
+
+class GzFile(C.Structure):
+    _fields_ = [("seq", C.c_void_p), ("seq_off", C.c_void_p), ("qual", C.c_void_p), ("qual_off", C.c_void_p), ("has_qual", C.c_void_p)]
+
+
+def gz_eof() -> bytes:
+    """cfr_gz_eof: the BGZF end-of-file member"""
+    p, n = C.POINTER(C.c_uint8)(), C.c_size_t()
+    lib().cfr_gz_eof(C.byref(p), C.byref(n))
+    return bytes(p[:n.value])
+
+
+def pack_strings(strings):
+    """byte strings -> (uint8 bytes back to back, uint64 offsets[n + 1])"""
+    off = np.zeros(len(strings) + 1, dtype=np.uint64)
+    if strings:
+        off[1:] = np.cumsum([len(s) for s in strings], dtype=np.uint64)
+    return np.frombuffer(b"".join(strings) or b"\0", dtype=np.uint8).copy(), off
+
+
+class Gz:
+    """cfr_gz: a text as BGZF members, and read dumps made and compressed in one call.  device=None: the host twin."""
+
+    def __init__(self, device=None, block_bytes=0, max_blocks=0, threads=0):
+        self._h = C.c_void_p()
+        o = GzOptions(block_bytes, max_blocks, threads, 0)
+        _check(lib().cfr_gz_open(C.c_int(-1 if device is None else device), C.byref(o), C.byref(self._h)))
+
+    def compress(self, text) -> bytes:
+        """the members of text (bytes or a uint8 array), without the end-of-file member"""
+        a = np.frombuffer(bytes(text) or b"\0", dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, dtype=np.uint8)
+        n = len(text)
+        out, out_n = C.POINTER(C.c_uint8)(), C.c_uint64()
+        _check(lib().cfr_gz_compress(self._h, _p(a), C.c_uint64(n), C.byref(out), C.byref(out_n)))
+        return C.string_at(out, out_n.value) if out_n.value else b""
+
+    def dump_arrays(self, id_bytes, id_off, select, files, copy=True):
+        """cfr_gz_dump on flat arrays: files is a list of (seq uint8, seq_off uint64[n + 1], qual uint8 or None, qual_off, has_qual uint8[n])
+        -> the members of every file (bytes; copy=False: their sizes only)"""
+        n = len(id_off) - 1
+        keep, arr = [_u8(id_bytes), _u64(id_off), _u8(select)], (GzFile * len(files))()
+        for k, (seq, seq_off, qual, qual_off, has_qual) in enumerate(files):
+            a = [_u8(seq), _u64(seq_off), _u8(qual), _u64(qual_off), _u8(has_qual)]
+            keep += a
+            arr[k].seq, arr[k].seq_off = a[0].ctypes.data, a[1].ctypes.data
+            if qual is not None:
+                arr[k].qual, arr[k].qual_off, arr[k].has_qual = a[2].ctypes.data, a[3].ctypes.data, a[4].ctypes.data
+        out, out_n = (C.POINTER(C.c_uint8) * len(files))(), (C.c_uint64 * len(files))()
+        _check(lib().cfr_gz_dump(self._h, _p(keep[0]), _p(keep[1]), _p(keep[2]), C.c_size_t(n), arr, C.c_int(len(files)), out, out_n))
+        if not copy:
+            return [int(out_n[k]) for k in range(len(files))]
+        return [C.string_at(out[k], out_n[k]) if out_n[k] else b"" for k in range(len(files))]
+
+    def dump(self, ids, select, files):
+        """ids: byte strings; select: n bytes; files: a list of (seqs, quals or None, has_qual or None), each a list of byte strings
+        (quals) or n bytes (has_qual) -> the members of every file, as a list of bytes"""
+        n = len(ids)
+        id_bytes, id_off = pack_strings([i.encode("latin-1") if isinstance(i, str) else bytes(i) for i in ids])
+        flat = []
+        for seqs, quals, has_qual in files:
+            sb, so = pack_strings(list(seqs))
+            qb, qo = pack_strings(list(quals)) if quals is not None else (None, None)
+            flat.append((sb, so, qb, qo, None if quals is None else (np.ascontiguousarray(has_qual, dtype=np.uint8) if n else np.zeros(1, dtype=np.uint8))))
+        return self.dump_arrays(id_bytes, id_off, np.ascontiguousarray(select, dtype=np.uint8) if n else np.zeros(1, dtype=np.uint8), flat)
+
+    def stats(self) -> GzStats:
+        st = GzStats()
+        _check(lib().cfr_gz_get_stats(self._h, C.byref(st)))
+        return st
+
+    def close(self):
+        if self._h:
+            lib().cfr_gz_close(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

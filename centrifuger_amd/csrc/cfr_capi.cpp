@@ -23,6 +23,7 @@
 #include "cfr_threads.hpp"
 #include "cfr_tokenize_core.hpp"
 #include "cfr_tsv.hpp"
+#include "cfr_gz.hpp"
 
 struct cfr_index { cfr::HostIndex *h; };
 struct cfr_read_format { cfr::ReadFormat f; };
@@ -38,6 +39,7 @@ struct cfr_promote { cfr::Promote *p; };
 struct cfr_kreport { cfr::Kreport *k; };
 struct cfr_tokenizer { cfr::Tokenizer *t; };
 struct cfr_tsv { cfr::Tsv *t; };
+struct cfr_gz { cfr::Gz *g; };
 struct cfr_quant { cfr::Quant *q; std::vector<double> weight; int32_t rounds = 0; bool ran = false; };
 // One call at a time per device image: `busy` is held for the length of every entry that touches the image (try_lock:
 // CFR_ERR_BUSY for the second caller) and by the worker thread while it runs a submitted batch.
@@ -108,6 +110,14 @@ std::set<const cfr_tsv *> g_tsv_live;
 bool tsv_live(const cfr_tsv *h) {
   std::lock_guard<std::mutex> lk(g_tsv_mu);
   return h && g_tsv_live.count(h) != 0;
+}
+
+// ... and the cfr_gz handles
+std::mutex g_gz_mu;
+std::set<const cfr_gz *> g_gz_live;
+bool gz_live(const cfr_gz *h) {
+  std::lock_guard<std::mutex> lk(g_gz_mu);
+  return h && g_gz_live.count(h) != 0;
 }
 
 // entry guard: the image's buffers, streams and statistics belong to one call at a time
@@ -1071,6 +1081,58 @@ void cfr_tsv_close(cfr_tsv *t) {
   }
   delete t->t;
   delete t;
+}
+
+// ---- a text as BGZF members, the read dumps (cfr_gz_core.hpp) ----
+void cfr_gz_options_default(cfr_gz_options *o) { if (o) memset(o, 0, sizeof(*o)); }
+
+cfr_status cfr_gz_open(int device, const cfr_gz_options *o, cfr_gz **out) {
+  if (!out) return bad_arg("cfr_gz_open: null argument");
+  *out = nullptr;
+  if (device < -1) return bad_arg("cfr_gz_open: device is a HIP ordinal, or -1 for the host twin");
+  cfr_gz_options opt{};
+  if (o) opt = *o;
+  return guarded([&]() -> cfr_status {
+    (void)cfr::gz_block_bytes(opt);
+    std::unique_ptr<cfr_gz> h(new cfr_gz{nullptr});
+    h->g = device < 0 ? cfr::make_gz_host(opt) : cfr::make_gz_device(device, opt);
+    { std::lock_guard<std::mutex> lk(g_gz_mu); g_gz_live.insert(h.get()); }
+    *out = h.release();
+    return CFR_OK;
+  });
+}
+
+cfr_status cfr_gz_compress(cfr_gz *h, const void *text, uint64_t n, const uint8_t **out, uint64_t *out_n) {
+  if (!gz_live(h)) return bad_arg("cfr_gz_compress: not an open cfr_gz handle");
+  return guarded([&]() -> cfr_status { h->g->compress((const uint8_t *)text, n, out, out_n); return CFR_OK; });
+}
+
+cfr_status cfr_gz_dump(cfr_gz *h, const char *id_bytes, const uint64_t *id_off, const uint8_t *select, size_t n, const cfr_gz_file *files, int n_files,
+                       const uint8_t **out, uint64_t *out_n) {
+  if (!gz_live(h)) return bad_arg("cfr_gz_dump: not an open cfr_gz handle");
+  return guarded([&]() -> cfr_status { h->g->dump(id_bytes, id_off, select, n, files, n_files, out, out_n); return CFR_OK; });
+}
+
+void cfr_gz_eof(const uint8_t **bytes, size_t *n) {
+  static const uint8_t eof[cfr::kGzEofBytes] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  if (bytes) *bytes = eof;
+  if (n) *n = sizeof(eof);
+}
+
+cfr_status cfr_gz_get_stats(cfr_gz *h, cfr_gz_stats *st) {
+  if (!gz_live(h)) return bad_arg("cfr_gz_get_stats: not an open cfr_gz handle");
+  if (!st) return bad_arg("cfr_gz_get_stats: null argument");
+  h->g->stats(st);
+  return CFR_OK;
+}
+
+void cfr_gz_close(cfr_gz *h) {
+  {
+    std::lock_guard<std::mutex> lk(g_gz_mu);
+    if (!h || !g_gz_live.erase(h)) return;
+  }
+  delete h->g;
+  delete h;
 }
 
 cfr_status cfr_device_index_set_tsv(cfr_dev_index *d, int on) {

@@ -68,10 +68,11 @@ const char *kUsage =
     "\t--parse-threads INT: threads that parse plain single-end read files in pieces [min(-t,8); 1 = sequential reader]\n"
     "\t--gpu-parse: tokenise plain FASTA/FASTQ files (-u, -1/-2) on the GPU that classifies them; the run falls back to the host parsers, with one log line, for what that does not cover [host parsers]\n"
     "\t--gpu-format: make the TSV rows on the GPU that classified the reads (with --gpu-parse the read ids never leave it); the rows are formatted on the host, with one log line, for what that does not cover [host formatter]\n"
+    "\t--gpu-dump: make and compress the --un / --cl read dumps on the GPU that classified the reads; the files are BGZF (gzip in members of at most 64 KiB, read by every gunzip); --merge-readpair keeps the host writer, with one log line [host writer, zlib level 1]\n"
     "\t-h: print this usage message\n"
     "\t-v: print the version information and quit\n";
 
-enum { OPT_UN = 1000, OPT_CL, OPT_NO_DUST, OPT_MIN_HITLEN, OPT_HITK, OPT_SECONDARY, OPT_GPU, OPT_GPU_BATCH, OPT_GPU_THROUGHPUT, OPT_GPU_FASTLOAD, OPT_GPU_BALANCED, OPT_PARSE_THREADS, OPT_GPU_PARSE, OPT_GPU_FORMAT, OPT_EXPAND_TAXID, OPT_MERGE_READPAIR, OPT_QUANT, OPT_QUANT_FORMAT, OPT_PROMOTE, OPT_KREPORT, OPT_BARCODE, OPT_UMI, OPT_READ_FORMAT, OPT_BARCODE_WHITELIST, OPT_BARCODE_TRANSLATE, OPT_UNSUPPORTED };
+enum { OPT_UN = 1000, OPT_CL, OPT_NO_DUST, OPT_MIN_HITLEN, OPT_HITK, OPT_SECONDARY, OPT_GPU, OPT_GPU_BATCH, OPT_GPU_THROUGHPUT, OPT_GPU_FASTLOAD, OPT_GPU_BALANCED, OPT_PARSE_THREADS, OPT_GPU_PARSE, OPT_GPU_FORMAT, OPT_GPU_DUMP, OPT_EXPAND_TAXID, OPT_MERGE_READPAIR, OPT_QUANT, OPT_QUANT_FORMAT, OPT_PROMOTE, OPT_KREPORT, OPT_BARCODE, OPT_UMI, OPT_READ_FORMAT, OPT_BARCODE_WHITELIST, OPT_BARCODE_TRANSLATE, OPT_UNSUPPORTED };
 
 // Persistent workers for the dust and the format stage: a 256 k-read batch is 6 ms of work on 64 threads, less than
 // what starting 64 threads costs, so the threads are started once.
@@ -145,6 +146,7 @@ struct Options {
   bool balanced_profile = false;
   bool gpu_parse = false;              // --gpu-parse: cfr_tokenize on the device instead of SeqReader, where it applies
   bool gpu_format = false;             // --gpu-format: the rows of a batch made on the device (cfr_device_index_tsv_last), where it applies
+  bool gpu_dump = false;               // --gpu-dump: the --un / --cl dumps made and compressed on the device (cfr_gz_dump), where it applies
   // single-cell input (CentrifugerClass.cpp:374-381)
   std::vector<std::string> bc_files, um_files;
   std::string read_format, whitelist, translate;
@@ -156,17 +158,24 @@ struct Options {
   bool has_barcode = false, has_umi = false, bc_hd = false, um_hd = false, single_cell = false;
 };
 
-// gz read dumps (ResultWriter::SetOutputReads, ResultWriter.hpp:126-176)
+// the files of a read dump (ResultWriter::SetOutputReads, ResultWriter.hpp:126-176): slot 0 read 1, 1 read 2, 2 barcode, 3 UMI; "" - the
+// run does not write that one.  Always 'fa' for barcode and umi (ResultWriter.hpp:161-171).
+std::string dump_file_name(const std::string &prefix, int slot, bool mate, bool has_barcode, bool has_umi) {
+  switch (slot) {
+    case 0: return prefix + (mate ? "_1.fq.gz" : ".fq.gz");
+    case 1: return mate ? prefix + "_2.fq.gz" : "";
+    case 2: return has_barcode ? prefix + "_bc.fa.gz" : "";
+    default: return has_umi ? prefix + "_um.fa.gz" : "";
+  }
+}
+
+// gz read dumps written record by record on the host
 struct ReadDump {
-  gzFile fp[4] = {nullptr, nullptr, nullptr, nullptr};   // read 1, read 2, barcode, UMI
+  gzFile fp[4] = {nullptr, nullptr, nullptr, nullptr};
   void open(const std::string &prefix, bool mate, bool has_barcode, bool has_umi) {
-    if (has_barcode) fp[2] = gzopen((prefix + "_bc.fa.gz").c_str(), "w1");   // always 'fa' for barcode and umi (ResultWriter.hpp:161-171)
-    if (has_umi) fp[3] = gzopen((prefix + "_um.fa.gz").c_str(), "w1");
-    if (mate) {
-      fp[0] = gzopen((prefix + "_1.fq.gz").c_str(), "w1");
-      fp[1] = gzopen((prefix + "_2.fq.gz").c_str(), "w1");
-    } else {
-      fp[0] = gzopen((prefix + ".fq.gz").c_str(), "w1");
+    for (int k : {2, 3, 0, 1}) {
+      const std::string name = dump_file_name(prefix, k, mate, has_barcode, has_umi);
+      if (!name.empty()) fp[k] = gzopen(name.c_str(), "w1");
     }
   }
   // (gzprintf, like ResultWriter.hpp:254-265: zlib formats into its 8192-byte buffer and writes NOTHING for a record that does
@@ -178,6 +187,30 @@ struct ReadDump {
   }
   void put_extra(int k, const char *id, const char *s) { if (fp[k]) gzprintf(fp[k], ">%s\n%s\n", id, s); }   // ResultWriter.hpp:267-275
   void close() { for (auto &f : fp) if (f) { gzclose(f); f = nullptr; } }
+};
+
+// --gpu-dump: the same files taken as BGZF members from the device workers; close() ends each with the end-of-file member
+struct RawDump {
+  FILE *fp[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool on() const { return fp[0] != nullptr; }
+  void open(const std::string &prefix, bool mate, bool has_barcode, bool has_umi) {
+    for (int k = 0; k < 4; ++k) {
+      const std::string name = dump_file_name(prefix, k, mate, has_barcode, has_umi);
+      if (name.empty()) continue;
+      if (!(fp[k] = fopen(name.c_str(), "wb"))) { print_log("ERROR: cannot write %s (%s).", name.c_str(), strerror(errno)); exit(EXIT_FAILURE); }
+    }
+  }
+  void put(int k, const std::string &members) { if (fp[k] && !members.empty()) fwrite(members.data(), 1, members.size(), fp[k]); }
+  void close() {
+    const uint8_t *eof = nullptr;
+    size_t n = 0;
+    cfr_gz_eof(&eof, &n);
+    for (auto &f : fp) if (f) {
+      const bool ok = fwrite(eof, 1, n, f) == n;
+      if (fclose(f) != 0 || !ok) { print_log("ERROR: writing a read dump failed (%s).", strerror(errno)); exit(EXIT_FAILURE); }
+      f = nullptr;
+    }
+  }
 };
 
 // CFR_CLI_TIMING=1: per-stage busy seconds on stderr at exit (stage threads overlap, so they do not add up to the wall clock)
@@ -260,7 +293,7 @@ int parse_options(int argc, char *argv[], Options &opt) {
       {"consider-secondary", required_argument, 0, OPT_SECONDARY}, {"gpu", required_argument, 0, OPT_GPU},
       {"gpu-batch", required_argument, 0, OPT_GPU_BATCH}, {"gpu-throughput", no_argument, 0, OPT_GPU_THROUGHPUT},
       {"gpu-fast-load", no_argument, 0, OPT_GPU_FASTLOAD}, {"gpu-balanced", no_argument, 0, OPT_GPU_BALANCED},
-      {"parse-threads", required_argument, 0, OPT_PARSE_THREADS}, {"gpu-parse", no_argument, 0, OPT_GPU_PARSE}, {"gpu-format", no_argument, 0, OPT_GPU_FORMAT},
+      {"parse-threads", required_argument, 0, OPT_PARSE_THREADS}, {"gpu-parse", no_argument, 0, OPT_GPU_PARSE}, {"gpu-format", no_argument, 0, OPT_GPU_FORMAT}, {"gpu-dump", no_argument, 0, OPT_GPU_DUMP},
       {"sample-sheet", required_argument, 0, OPT_UNSUPPORTED}, {"merge-readpair", no_argument, 0, OPT_MERGE_READPAIR},
       {"quant", required_argument, 0, OPT_QUANT}, {"quant-format", required_argument, 0, OPT_QUANT_FORMAT},
       {"promote", required_argument, 0, OPT_PROMOTE}, {"kreport", required_argument, 0, OPT_KREPORT},
@@ -320,6 +353,7 @@ int parse_options(int argc, char *argv[], Options &opt) {
       case OPT_PARSE_THREADS: opt.parse_threads = atoi(optarg); break;
       case OPT_GPU_PARSE: opt.gpu_parse = true; break;
       case OPT_GPU_FORMAT: opt.gpu_format = true; break;
+      case OPT_GPU_DUMP: opt.gpu_dump = true; break;
       case OPT_UNSUPPORTED:
         print_log("ERROR: option --%s belongs to a part of Centrifuger outside the MI355X classification path and is not available in this build.",
                   long_options[option_index].name);
@@ -511,6 +545,9 @@ struct Run {
   StageClock clk;
   const std::chrono::steady_clock::time_point t_wall;
   ReadDump un, cl;
+  RawDump raw_un, raw_cl;              // --gpu-dump, where it applies: the same files, written as the devices' members
+  bool gpu_dump = false;
+  std::atomic<long long> dump_ns{0}, dump_kernel_ns{0};   // ... the workers' time in cfr_gz_dump, and the device time of its kernels
   bool gpu_parse = false;              // --gpu-parse, where it applies
   bool gpu_format = false;             // --gpu-format, where it applies
   std::atomic<long long> tsv_kernel_ns{0};   // ... and the device time of its kernels (cfr_last_tsv_ms), all batches
@@ -917,6 +954,10 @@ struct DeviceWorker {
   std::vector<char> id_bytes;                           // --gpu-format: the batch's ids without their terminators, and their n + 1 offsets
   std::vector<uint64_t> id_offs;
   size_t tsv_guess = 1 << 16;                           // ... and the size the text buffer starts with: the largest text so far, and a little
+  cfr_gz *gz = nullptr;                                 // --gpu-dump: opened with the first batch, on this worker's GPU
+  std::vector<uint8_t> dump_select;
+  std::vector<char> dump_ids, dump_extra[2];
+  std::vector<uint64_t> dump_id_off, dump_extra_off[2];
 
   // --gpu-parse: a raw batch on the worker's own tokeniser(s).  true: the reads are in HBM (ids in b.ids); false: the piece is not
   // regular, nothing was taken from it
@@ -1053,6 +1094,58 @@ struct DeviceWorker {
     if (cfr_last_tsv_ms(dev, &ms) == CFR_OK) run.tsv_kernel_ns += (long long)((double)ms * 1e6);
   }
 
+  // --gpu-dump: the records of the batch's classified and unclassified reads made and compressed on this worker's GPU, from the arrays
+  // write_stage prints them from (masked bases, as the dust stage left them); the members wait on the batch for the writer
+  void dump_on_device(Batch &b) {
+    const Options &opt = run.opt;
+    b.dump_device = true;
+    for (auto &set : b.dump_parts) for (auto &s : set) s.clear();
+    if (!b.n) return;
+    if (!gz) { const cfr_status s = cfr_gz_open(opt.gpus[dev_no], nullptr, &gz); if (s != CFR_OK) die_status("cfr_gz_open", s); }
+    static const char kNone[1] = {0};
+    auto strings = [&](const std::vector<char> &text, const std::vector<size_t> &at, std::vector<char> &bytes, std::vector<uint64_t> &off) {   // NUL-terminated -> bytes + offsets
+      bytes.clear(); off.clear();
+      for (size_t i = 0; i < b.n; ++i) {
+        const char *s = text.data() + at[i];
+        off.push_back(bytes.size());
+        bytes.insert(bytes.end(), s, s + strlen(s));
+      }
+      off.push_back(bytes.size());
+    };
+    strings(b.ids, b.id_off, dump_ids, dump_id_off);
+    cfr_gz_file files[4];
+    int slot_of[4], n_files = 0;
+    auto reads = [&](int slot, const ByteBuf &bases, const std::vector<uint64_t> &offs, const std::vector<char> &qual, const std::vector<size_t> &q_off, const std::vector<uint8_t> &has) {
+      static_assert(sizeof(size_t) == sizeof(uint64_t), "the quality offsets are handed over as they are");
+      files[n_files] = cfr_gz_file{bases.data(), offs.data(), qual.empty() ? kNone : qual.data(), reinterpret_cast<const uint64_t *>(q_off.data()), has.data()};
+      slot_of[n_files++] = slot;
+    };
+    reads(0, b.bases1, b.offs1, b.qual1, b.q1_off, b.has_qual);
+    if (b.paired) reads(1, b.bases2, b.offs2, b.qual2, b.q2_off, b.has_qual2);
+    if (opt.has_barcode) {
+      strings(b.bc_str, b.bc_str_off, dump_extra[0], dump_extra_off[0]);
+      files[n_files] = cfr_gz_file{(const uint8_t *)dump_extra[0].data(), dump_extra_off[0].data(), nullptr, nullptr, nullptr};
+      slot_of[n_files++] = 2;
+    }
+    if (opt.has_umi) {
+      strings(b.um_str, b.um_str_off, dump_extra[1], dump_extra_off[1]);
+      files[n_files] = cfr_gz_file{(const uint8_t *)dump_extra[1].data(), dump_extra_off[1].data(), nullptr, nullptr, nullptr};
+      slot_of[n_files++] = 3;
+    }
+    dump_select.resize(b.n);
+    for (int set = 0; set < 2; ++set) {                 // 0: --un, 1: --cl
+      if (!(set ? run.raw_cl.on() : run.raw_un.on())) continue;
+      for (size_t i = 0; i < b.n; ++i) dump_select[i] = (b.results[i].n_match > 0) == (set == 1) ? 1 : 0;
+      const uint8_t *out[4];
+      uint64_t out_n[4];
+      const cfr_status s = cfr_gz_dump(gz, dump_ids.data(), dump_id_off.data(), dump_select.data(), b.n, files, n_files, out, out_n);
+      if (s != CFR_OK) die_status("cfr_gz_dump", s);
+      for (int f = 0; f < n_files; ++f) b.dump_parts[set][slot_of[f]].assign((const char *)out[f], out_n[f]);
+      cfr_gz_stats st;
+      if (cfr_gz_get_stats(gz, &st) == CFR_OK) run.dump_kernel_ns += (long long)((double)(st.format_ms + st.deflate_ms + st.pack_ms) * 1e6);
+    }
+  }
+
   void operator()() {
     while (std::shared_ptr<Batch> b = run.dusted.pop()) {
       auto ts = tick();
@@ -1070,8 +1163,14 @@ struct DeviceWorker {
         format_on_device(*b, resident);
         run.clk.add(T_FORMAT, ts);
       }
+      if (run.gpu_dump) {
+        ts = tick();
+        dump_on_device(*b);
+        run.dump_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(tick() - ts).count();
+      }
       run.classified.push(b);
     }
+    cfr_gz_close(gz);
     cfr_tokenizer_close(tok1);
     cfr_tokenizer_close(tok2);
     run.classified.close();
@@ -1133,7 +1232,9 @@ void write_stage(Run &run) {
     const auto tw = tick();
     for (size_t t = 0; t < b->n_parts; ++t) { fwrite(b->tsv_parts[t].data(), 1, b->tsv_parts[t].size(), stdout); run.classified_reads += b->part_hits[t]; }
     run.total += b->n;
-    if (cl.fp[0] || un.fp[0]) for (size_t i = 0; i < b->n; ++i) {
+    if (b->dump_device) {                    // --gpu-dump: the device worker made the members of every file
+      for (int k = 0; k < 4; ++k) { run.raw_un.put(k, b->dump_parts[0][k]); run.raw_cl.put(k, b->dump_parts[1][k]); }
+    } else if (cl.fp[0] || un.fp[0]) for (size_t i = 0; i < b->n; ++i) {
       const bool hit = b->results[i].n_match > 0;
       ReadDump *dump = hit ? (cl.fp[0] ? &cl : nullptr) : (un.fp[0] ? &un : nullptr);
       if (!dump) continue;
@@ -1159,8 +1260,22 @@ void write_stage(Run &run) {
 // ---- what is decided before any stage starts: the devices, the dumps, which stages work on the host -----------------------------
 int plan_run(Run &run) {
   Options &opt = run.opt;
-  if (!opt.un_prefix.empty()) run.un.open(opt.un_prefix, opt.paired, opt.has_barcode, opt.has_umi);
-  if (!opt.cl_prefix.empty()) run.cl.open(opt.cl_prefix, opt.paired, opt.has_barcode, opt.has_umi);
+  // ---- --gpu-dump: the dumps are made and compressed by the device workers; the rule of --gpu-parse and --gpu-format for what is not covered
+  run.gpu_dump = opt.gpu_dump;
+  if (run.gpu_dump) {
+    if (opt.un_prefix.empty() && opt.cl_prefix.empty()) { print_log("--gpu-dump has no effect: neither --un nor --cl is given."); run.gpu_dump = false; }
+    else if (opt.merge) {
+      print_log("--gpu-dump is not used, the dumps are written on the host: --merge-readpair takes every mate from one of two buffers.");
+      run.gpu_dump = false;
+    }
+  }
+  if (run.gpu_dump) {
+    if (!opt.un_prefix.empty()) run.raw_un.open(opt.un_prefix, opt.paired, opt.has_barcode, opt.has_umi);
+    if (!opt.cl_prefix.empty()) run.raw_cl.open(opt.cl_prefix, opt.paired, opt.has_barcode, opt.has_umi);
+  } else {
+    if (!opt.un_prefix.empty()) run.un.open(opt.un_prefix, opt.paired, opt.has_barcode, opt.has_umi);
+    if (!opt.cl_prefix.empty()) run.cl.open(opt.cl_prefix, opt.paired, opt.has_barcode, opt.has_umi);
+  }
   if (!opt.all_gpus && opt.gpus.empty()) { print_log("ERROR: no MI355X device selected."); return EXIT_FAILURE; }
   if (opt.all_gpus) {
     int cnt = 0;
@@ -1271,6 +1386,8 @@ void load_index_and_devices(Run &run) {
   const Options &opt = run.opt;
   run.un.close();
   run.cl.close();
+  run.raw_un.close();
+  run.raw_cl.close();
   fflush(stdout);
   // ResultWriter::Finalize (ResultWriter.hpp:279-283)
   print_log("Processed %lu read fragments, and %lu (%.2lf%%) can be classified.", (unsigned long)run.total, (unsigned long)run.classified_reads,
@@ -1310,6 +1427,10 @@ void load_index_and_devices(Run &run) {
     static const char *names[] = {"index_open", "device_index", "parse", "dust", "classify", "format", "write", "wall"};
     for (int k = 0; k < 8; ++k) fprintf(stderr, "[timing] %-12s %8.3f s\n", names[k], (double)run.clk.ns[k].load() * 1e-9);
     if (run.gpu_format) fprintf(stderr, "[timing] %-12s %8.3f s\n", "tsv_kernels", (double)run.tsv_kernel_ns.load() * 1e-9);
+    if (run.gpu_dump) {
+      fprintf(stderr, "[timing] %-12s %8.3f s\n", "dump", (double)run.dump_ns.load() * 1e-9);
+      fprintf(stderr, "[timing] %-12s %8.3f s\n", "dump_kernels", (double)run.dump_kernel_ns.load() * 1e-9);
+    }
   }
   // the TSV must have reached its destination before success is reported (a full disk or a closed pipe otherwise ends in a
   // truncated file with exit status 0); only then is the runtime's teardown skipped (~0.3 s of a sub-second run)

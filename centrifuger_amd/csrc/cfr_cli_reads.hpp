@@ -591,6 +591,8 @@ struct Batch {
   std::vector<size_t> part_hits;       //  the strings keep their capacity across recycling); classified reads per part
   size_t n_parts = 0;
   bool tsv_device = false;             // --gpu-format: tsv_parts[0] is the whole batch, made on the device
+  bool dump_device = false;            // --gpu-dump: dump_parts hold the batch's BGZF members, made on the device
+  std::string dump_parts[2][4];        //  [0: --un, 1: --cl][read 1, read 2, barcode, UMI]
   bool done = false;
   // --gpu-parse: the piece(s) of the mapped read file(s) this batch stands for, not parsed yet: the device worker tokenises them
   // (cfr_tokenize) or, when they are not regular, parses them with SeqReader.  raw_want: the records the piece was cut for;
@@ -600,7 +602,7 @@ struct Batch {
   size_t raw1_len = 0, raw2_len = 0, raw_want = 0, raw_first = 0;
   const char *id(size_t i) const { return ids.data() + id_off[i]; }
   void reset(bool pair) {   // keeps every buffer's capacity: batches are recycled, so steady state allocates (and page-faults) nothing
-    n = 0; done = false; tsv_device = false; raw = false; raw1 = raw2 = nullptr; raw1_len = raw2_len = raw_want = raw_first = 0;
+    n = 0; done = false; tsv_device = false; dump_device = false; raw = false; raw1 = raw2 = nullptr; raw1_len = raw2_len = raw_want = raw_first = 0;
     ids.clear(); id_off.clear(); qual1.clear(); qual2.clear(); q1_off.clear(); q2_off.clear(); has_qual.clear(); has_qual2.clear();
     bases1.clear(); bases2.clear(); offs1.clear(); offs2.clear(); n_parts = 0;
     bc_raw.clear(); um_raw.clear(); bc_rawq.clear(); um_rawq.clear(); bc_cm.clear(); um_cm.clear(); r1_cm.clear();

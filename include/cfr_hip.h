@@ -612,6 +612,40 @@ cfr_status cfr_device_index_tsv_last_resident(cfr_dev_index *d, const void *d_te
 cfr_status cfr_tokenizer_device_records(cfr_tokenizer *t, const void **d_text, const void **d_records);   /* device handle only; valid until the next cfr_tokenize / close */
 cfr_status cfr_last_tsv_ms(const cfr_dev_index *d, float *ms);
 
+/* ---- a text as BGZF members, and the --un / --cl read dumps made and compressed in one call (ResultWriter::OutputRead,
+ * ResultWriter.hpp:254-275, for a batch at once; the framing, the encoder and the records are stated in csrc/cfr_gz_core.hpp) ----
+ * BGZF is gzip cut into members of at most 64 KiB, each with its size in an extra field: every gunzip reads the concatenation, and
+ * readers that know the field inflate the members in parallel.  The bytes are NOT those of zlib; what they inflate to is the contract.
+ * cfr_gz_open: device >= 0: the kernels of cfr_gz.hip on that GPU (CFR_ERR_NO_DEVICE without it: no fall-back); device = -1: the host
+ *   twin on `threads` host threads, the same bytes.  options (NULL = defaults; a field of 0 = its default): block_bytes - the input
+ *   bytes per member, 1 .. 65280 (the default, htslib's); max_blocks - at most that many workgroups per kernel.  Both exist for the tests.
+ * cfr_gz_compress: host text in; *out points at the members, back to back, in a buffer the handle owns until its next call.  No
+ *   end-of-file member.  n = 0 gives *out_n = 0.
+ * cfr_gz_dump: one call makes the text of up to 4 files and compresses each; on the device the text never exists on the host.  Read i
+ *   has id id_bytes[id_off[i], id_off[i + 1]) in every file; select[i] = 0 leaves it out.  Its record in file f is
+ *   ">id\nseq\n", or "@id\nseq\n+\nqual\n" where files[f].qual is not NULL and files[f].has_qual[i] is not 0.  A record of 8192 bytes
+ *   or more is left out of that file alone (what gzprintf does with it).  out / out_n: n_files entries, as for cfr_gz_compress.
+ * cfr_gz_eof: the 28-byte end-of-file member, to be written once behind the last member of a file (a file of it alone is an empty text).
+ * cfr_gz_get_stats: the last call: device times from events (host twin: wall times of making the text and of compressing it in
+ *   format_ms and deflate_ms), summed over the files of a dump; blocks = members, stored_blocks = those that hold a stored block.
+ * A handle is used by one thread at a time. */
+typedef struct cfr_gz cfr_gz;
+typedef struct { int32_t block_bytes, max_blocks, threads, pad; } cfr_gz_options;
+typedef struct { float upload_ms, format_ms, deflate_ms, pack_ms, download_ms; uint32_t pad; uint64_t blocks, stored_blocks, bytes_in, bytes_out; } cfr_gz_stats;
+typedef struct {
+  const uint8_t *seq; const uint64_t *seq_off;      /* n + 1 offsets */
+  const char *qual; const uint64_t *qual_off;       /* NULL, or n + 1 offsets */
+  const uint8_t *has_qual;                          /* n bytes; may be NULL when qual is */
+} cfr_gz_file;
+void cfr_gz_options_default(cfr_gz_options *o);
+cfr_status cfr_gz_open(int device, const cfr_gz_options *o, cfr_gz **out);
+cfr_status cfr_gz_compress(cfr_gz *h, const void *text, uint64_t n, const uint8_t **out, uint64_t *out_n);
+cfr_status cfr_gz_dump(cfr_gz *h, const char *id_bytes, const uint64_t *id_off, const uint8_t *select, size_t n,
+                       const cfr_gz_file *files, int n_files, const uint8_t **out, uint64_t *out_n);
+void cfr_gz_eof(const uint8_t **bytes, size_t *n);
+cfr_status cfr_gz_get_stats(cfr_gz *h, cfr_gz_stats *st);
+void cfr_gz_close(cfr_gz *h);
+
 /* ---- single-cell input: read formats, barcode whitelist, barcode translation (ReadFormatter.hpp, BarcodeCorrector.hpp,
  * BarcodeTranslator.hpp; the flow of CentrifugerClass.cpp:163-224, :565-574) ----
  * Handles of their own, independent of any cfr_dev_index; one call at a time per handle.  Barcodes, reads and comments are flat
