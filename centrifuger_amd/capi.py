@@ -1185,13 +1185,16 @@ class Tsv:
             pass
 
 
+GZ_CODES = {"fixed": 0, "dynamic": 1}
+
+
 class GzOptions(C.Structure):
-    _fields_ = [("block_bytes", C.c_int32), ("max_blocks", C.c_int32), ("threads", C.c_int32), ("pad", C.c_int32)]
+    _fields_ = [("block_bytes", C.c_int32), ("max_blocks", C.c_int32), ("threads", C.c_int32), ("codes", C.c_int32)]
 
 
 class GzStats(C.Structure):
     _fields_ = [("upload_ms", C.c_float), ("format_ms", C.c_float), ("deflate_ms", C.c_float), ("pack_ms", C.c_float), ("download_ms", C.c_float),
-                ("pad", C.c_uint32), ("blocks", C.c_uint64), ("stored_blocks", C.c_uint64), ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64)]
+                ("dynamic_blocks", C.c_uint32), ("blocks", C.c_uint64), ("stored_blocks", C.c_uint64), ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64)]
 
 
 class GzFile(C.Structure):
@@ -1214,11 +1217,17 @@ def pack_strings(strings):
 
 
 class Gz:
-    """cfr_gz: a text as BGZF members, and read dumps made and compressed in one call.  device=None: the host twin."""
+    """cfr_gz: a text as BGZF members, and read dumps made and compressed in one call.  device=None: the host twin.
+    codes: "fixed" (the fixed Huffman code, or stored) or "dynamic" (each block's own codes where they are smaller); an integer goes
+    to cfr_gz_options.codes as it is."""
 
-    def __init__(self, device=None, block_bytes=0, max_blocks=0, threads=0):
+    def __init__(self, device=None, block_bytes=0, max_blocks=0, threads=0, codes="fixed"):
         self._h = C.c_void_p()
-        o = GzOptions(block_bytes, max_blocks, threads, 0)
+        if isinstance(codes, str):
+            if codes not in GZ_CODES:
+                raise ValueError("codes is 'fixed' or 'dynamic'")
+            codes = GZ_CODES[codes]
+        o = GzOptions(block_bytes, max_blocks, threads, codes)
         _check(lib().cfr_gz_open(C.c_int(-1 if device is None else device), C.byref(o), C.byref(self._h)))
 
     def compress(self, text) -> bytes:

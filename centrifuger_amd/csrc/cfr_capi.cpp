@@ -1094,6 +1094,7 @@ cfr_status cfr_gz_open(int device, const cfr_gz_options *o, cfr_gz **out) {
   if (o) opt = *o;
   return guarded([&]() -> cfr_status {
     (void)cfr::gz_block_bytes(opt);
+    (void)cfr::gz_dynamic(opt);
     std::unique_ptr<cfr_gz> h(new cfr_gz{nullptr});
     h->g = device < 0 ? cfr::make_gz_host(opt) : cfr::make_gz_device(device, opt);
     { std::lock_guard<std::mutex> lk(g_gz_mu); g_gz_live.insert(h.get()); }

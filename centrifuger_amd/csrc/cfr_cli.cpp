@@ -69,10 +69,11 @@ const char *kUsage =
     "\t--gpu-parse: tokenise plain FASTA/FASTQ files (-u, -1/-2) on the GPU that classifies them; the run falls back to the host parsers, with one log line, for what that does not cover [host parsers]\n"
     "\t--gpu-format: make the TSV rows on the GPU that classified the reads (with --gpu-parse the read ids never leave it); the rows are formatted on the host, with one log line, for what that does not cover [host formatter]\n"
     "\t--gpu-dump: make and compress the --un / --cl read dumps on the GPU that classified the reads; the files are BGZF (gzip in members of at most 64 KiB, read by every gunzip); --merge-readpair keeps the host writer, with one log line [host writer, zlib level 1]\n"
+    "\t--gpu-dump-codes fixed|dynamic: the Huffman codes of --gpu-dump's members: the fixed code of deflate, or each member's own codes where they make it smaller (smaller files, more work on the GPU) [fixed]\n"
     "\t-h: print this usage message\n"
     "\t-v: print the version information and quit\n";
 
-enum { OPT_UN = 1000, OPT_CL, OPT_NO_DUST, OPT_MIN_HITLEN, OPT_HITK, OPT_SECONDARY, OPT_GPU, OPT_GPU_BATCH, OPT_GPU_THROUGHPUT, OPT_GPU_FASTLOAD, OPT_GPU_BALANCED, OPT_PARSE_THREADS, OPT_GPU_PARSE, OPT_GPU_FORMAT, OPT_GPU_DUMP, OPT_EXPAND_TAXID, OPT_MERGE_READPAIR, OPT_QUANT, OPT_QUANT_FORMAT, OPT_PROMOTE, OPT_KREPORT, OPT_BARCODE, OPT_UMI, OPT_READ_FORMAT, OPT_BARCODE_WHITELIST, OPT_BARCODE_TRANSLATE, OPT_UNSUPPORTED };
+enum { OPT_UN = 1000, OPT_CL, OPT_NO_DUST, OPT_MIN_HITLEN, OPT_HITK, OPT_SECONDARY, OPT_GPU, OPT_GPU_BATCH, OPT_GPU_THROUGHPUT, OPT_GPU_FASTLOAD, OPT_GPU_BALANCED, OPT_PARSE_THREADS, OPT_GPU_PARSE, OPT_GPU_FORMAT, OPT_GPU_DUMP, OPT_GPU_DUMP_CODES, OPT_EXPAND_TAXID, OPT_MERGE_READPAIR, OPT_QUANT, OPT_QUANT_FORMAT, OPT_PROMOTE, OPT_KREPORT, OPT_BARCODE, OPT_UMI, OPT_READ_FORMAT, OPT_BARCODE_WHITELIST, OPT_BARCODE_TRANSLATE, OPT_UNSUPPORTED };
 
 // Persistent workers for the dust and the format stage: a 256 k-read batch is 6 ms of work on 64 threads, less than
 // what starting 64 threads costs, so the threads are started once.
@@ -146,6 +147,7 @@ struct Options {
   bool balanced_profile = false;
   bool gpu_parse = false;              // --gpu-parse: cfr_tokenize on the device instead of SeqReader, where it applies
   bool gpu_format = false;             // --gpu-format: the rows of a batch made on the device (cfr_device_index_tsv_last), where it applies
+  bool gpu_dump_dynamic = false;       // --gpu-dump-codes dynamic: cfr_gz_options.codes = 1 for those dumps
   bool gpu_dump = false;               // --gpu-dump: the --un / --cl dumps made and compressed on the device (cfr_gz_dump), where it applies
   // single-cell input (CentrifugerClass.cpp:374-381)
   std::vector<std::string> bc_files, um_files;
@@ -293,7 +295,7 @@ int parse_options(int argc, char *argv[], Options &opt) {
       {"consider-secondary", required_argument, 0, OPT_SECONDARY}, {"gpu", required_argument, 0, OPT_GPU},
       {"gpu-batch", required_argument, 0, OPT_GPU_BATCH}, {"gpu-throughput", no_argument, 0, OPT_GPU_THROUGHPUT},
       {"gpu-fast-load", no_argument, 0, OPT_GPU_FASTLOAD}, {"gpu-balanced", no_argument, 0, OPT_GPU_BALANCED},
-      {"parse-threads", required_argument, 0, OPT_PARSE_THREADS}, {"gpu-parse", no_argument, 0, OPT_GPU_PARSE}, {"gpu-format", no_argument, 0, OPT_GPU_FORMAT}, {"gpu-dump", no_argument, 0, OPT_GPU_DUMP},
+      {"parse-threads", required_argument, 0, OPT_PARSE_THREADS}, {"gpu-parse", no_argument, 0, OPT_GPU_PARSE}, {"gpu-format", no_argument, 0, OPT_GPU_FORMAT}, {"gpu-dump", no_argument, 0, OPT_GPU_DUMP}, {"gpu-dump-codes", required_argument, 0, OPT_GPU_DUMP_CODES},
       {"sample-sheet", required_argument, 0, OPT_UNSUPPORTED}, {"merge-readpair", no_argument, 0, OPT_MERGE_READPAIR},
       {"quant", required_argument, 0, OPT_QUANT}, {"quant-format", required_argument, 0, OPT_QUANT_FORMAT},
       {"promote", required_argument, 0, OPT_PROMOTE}, {"kreport", required_argument, 0, OPT_KREPORT},
@@ -354,6 +356,11 @@ int parse_options(int argc, char *argv[], Options &opt) {
       case OPT_GPU_PARSE: opt.gpu_parse = true; break;
       case OPT_GPU_FORMAT: opt.gpu_format = true; break;
       case OPT_GPU_DUMP: opt.gpu_dump = true; break;
+      case OPT_GPU_DUMP_CODES:
+        if (!strcmp(optarg, "dynamic")) opt.gpu_dump_dynamic = true;
+        else if (!strcmp(optarg, "fixed")) opt.gpu_dump_dynamic = false;
+        else { print_log("ERROR: --gpu-dump-codes is 'fixed' or 'dynamic', not '%s'.", optarg); return EXIT_FAILURE; }
+        break;
       case OPT_UNSUPPORTED:
         print_log("ERROR: option --%s belongs to a part of Centrifuger outside the MI355X classification path and is not available in this build.",
                   long_options[option_index].name);
@@ -1101,7 +1108,13 @@ struct DeviceWorker {
     b.dump_device = true;
     for (auto &set : b.dump_parts) for (auto &s : set) s.clear();
     if (!b.n) return;
-    if (!gz) { const cfr_status s = cfr_gz_open(opt.gpus[dev_no], nullptr, &gz); if (s != CFR_OK) die_status("cfr_gz_open", s); }
+    if (!gz) {
+      cfr_gz_options gz_opt;
+      cfr_gz_options_default(&gz_opt);
+      gz_opt.codes = opt.gpu_dump_dynamic ? 1 : 0;
+      const cfr_status s = cfr_gz_open(opt.gpus[dev_no], &gz_opt, &gz);
+      if (s != CFR_OK) die_status("cfr_gz_open", s);
+    }
     static const char kNone[1] = {0};
     auto strings = [&](const std::vector<char> &text, const std::vector<size_t> &at, std::vector<char> &bytes, std::vector<uint64_t> &off) {   // NUL-terminated -> bytes + offsets
       bytes.clear(); off.clear();
@@ -1269,6 +1282,7 @@ int plan_run(Run &run) {
       run.gpu_dump = false;
     }
   }
+  if (opt.gpu_dump_dynamic && !run.gpu_dump) { print_log("--gpu-dump-codes dynamic has no effect: the dumps are not made on the GPU."); opt.gpu_dump_dynamic = false; }
   if (run.gpu_dump) {
     if (!opt.un_prefix.empty()) run.raw_un.open(opt.un_prefix, opt.paired, opt.has_barcode, opt.has_umi);
     if (!opt.cl_prefix.empty()) run.raw_cl.open(opt.cl_prefix, opt.paired, opt.has_barcode, opt.has_umi);

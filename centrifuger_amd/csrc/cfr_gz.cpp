@@ -23,6 +23,11 @@ uint32_t gz_block_bytes(const cfr_gz_options &o) {
   return o.block_bytes ? (uint32_t)o.block_bytes : kGzBlockMax;
 }
 
+bool gz_dynamic(const cfr_gz_options &o) {
+  if (o.codes != 0 && o.codes != 1) throw std::invalid_argument("cfr_gz_open: codes is 0 (fixed Huffman codes) or 1 (dynamic)");
+  return o.codes == 1;
+}
+
 void gz_check_dump(const char *id_bytes, const uint64_t *id_off, const uint8_t *select, size_t n, const cfr_gz_file *files, int n_files,
                    const uint8_t *const *out, const uint64_t *out_n) {
   if (n_files < 1 || n_files > kGzMaxFiles) throw std::invalid_argument("cfr_gz_dump: n_files is 1 .. 4");
@@ -63,18 +68,20 @@ struct BitSink {            // the stream's bits into bytes, least significant b
   void flush() { if (have) { *p++ = (uint8_t)acc; acc = 0; have = 0; } }
 };
 
-// one block into its slot (the member begins at slot + 2); returns the member's bytes
-uint32_t encode_block(const uint8_t *in, uint32_t n, uint8_t *slot, std::vector<uint32_t> &table, const CrcTable &crc_table, bool &stored) {
+// one block into its slot (the member begins at slot + 2); returns the member's bytes.  kind: 0 stored, 1 fixed, 2 dynamic.
+// tokens: nullptr in fixed mode, else room for n tokens: they are kept, counted and written once the choice is made.
+uint32_t encode_block(const uint8_t *in, uint32_t n, uint8_t *slot, std::vector<uint32_t> &table, const CrcTable &crc_table, uint32_t *tokens, uint32_t &kind) {
   uint8_t *member = slot + 2, *def = member + kGzHeader;
   std::fill(table.begin(), table.end(), 0u);
   uint32_t mlen[kGzWindow], mdist[kGzWindow];
   uint64_t tok_bits[kGzWindow];
   uint32_t tok_nb[kGzWindow];
+  uint32_t lfreq[kGzLitSyms] = {0}, dfreq[kGzDistSyms] = {0};
   BitSink sink{def};
-  sink.put(3, kGzFirstBits);
+  if (!tokens) sink.put(3, kGzFirstBits);
   uint64_t bitpos = kGzFirstBits;
-  uint32_t next_free = 0;
-  stored = false;
+  uint32_t next_free = 0, n_kept = 0;
+  bool stored = false;
   for (uint32_t base = 0; base < n; base += kGzWindow) {
     const uint32_t end = std::min(base + kGzWindow, n);
     for (uint32_t p = base; p < end; ++p) {                 // 1. lookup: the table as the earlier windows left it
@@ -89,21 +96,60 @@ uint32_t encode_block(const uint8_t *in, uint32_t n, uint8_t *slot, std::vector<
     uint32_t pos = std::max(next_free, base);
     while (pos < end) {
       const uint32_t k = pos - base;
-      tok_nb[n_tok] = mlen[k] ? gz_match(mlen[k], mdist[k], tok_bits[n_tok]) : gz_literal(in[pos], tok_bits[n_tok]);
-      total += tok_nb[n_tok++];
+      if (tokens) {                                         // dynamic mode: count and keep
+        uint32_t eb, ev;
+        if (mlen[k]) {
+          ++lfreq[gz_len_symbol(mlen[k], eb, ev)];
+          ++dfreq[gz_dist_symbol(mdist[k], eb, ev)];
+          tokens[n_kept++] = gz_token_match(mlen[k], mdist[k]);
+        } else {
+          ++lfreq[in[pos]];
+          tokens[n_kept++] = in[pos];
+        }
+      } else {
+        tok_nb[n_tok] = mlen[k] ? gz_match(mlen[k], mdist[k], tok_bits[n_tok]) : gz_literal(in[pos], tok_bits[n_tok]);
+        total += tok_nb[n_tok++];
+      }
       pos += mlen[k] ? mlen[k] : 1;
     }
     next_free = pos;
+    if (tokens) continue;
     if (gz_must_store(bitpos + total, n)) { stored = true; break; }
     for (uint32_t t = 0; t < n_tok; ++t) sink.put(tok_bits[t], tok_nb[t]);   // 4. emit
     bitpos += total;
   }
-  uint32_t def_bytes;
-  if (stored) {
+  uint32_t def_bytes = 0;
+  if (tokens) {
+    ++lfreq[kGzEob];
+    uint32_t ltab[kGzLitSyms], dtab[kGzDistSyms], clfreq[kGzClSyms], cltab[kGzClSyms], w32[kGzLitSyms];
+    uint8_t lens[kGzLitSyms + kGzDistSyms], cllen[kGzClSyms];
+    uint16_t w16[kGzLitSyms], cnt[16];
+    const GzDynWork w{lfreq, dfreq, ltab, dtab, clfreq, cltab, lens, cllen, w32, w16, cnt};
+    const GzDynPlan plan = gz_dyn_build(w);
+    kind = gz_choose(n, plan);
+    if (kind) {
+      GzWordSink words{def, 0, 0};
+      if (kind == 2) gz_put_dyn_header(words, w, plan);
+      else {
+        words.put(3, kGzFirstBits);
+        for (uint32_t s = 0; s < kGzLitSyms; ++s) ltab[s] = gz_fixed_entry(s);
+        for (uint32_t d = 0; d < kGzDistSyms; ++d) dtab[d] = gz_fixed_dist_entry(d);
+      }
+      for (uint32_t t = 0; t <= n_kept; ++t) {              // (the end-of-block symbol behind the last token)
+        uint64_t bits;
+        const uint32_t nb = gz_token_bits(t < n_kept ? tokens[t] : kGzEob, ltab, dtab, bits);
+        words.put(bits & 0xffffffffu, std::min(nb, 32u));
+        if (nb > 32) words.put(bits >> 32, nb - 32);
+      }
+      def_bytes = ((kind == 2 ? plan.dyn_bits : plan.fixed_bits) + 7) >> 3;
+      for (uint32_t k = 0; k * 8 < words.have; ++k) words.p[k] = (uint8_t)(words.acc >> (8 * k));
+    }
+  } else kind = stored ? 0 : 1;
+  if (kind == 0) {
     gz_put_stored_head(def, n);
     memcpy(def + kGzStoredHead, in, n);
     def_bytes = kGzStoredHead + n;
-  } else {
+  } else if (!tokens) {
     sink.put(0, kGzEndBits);
     sink.flush();
     def_bytes = (uint32_t)((bitpos + kGzEndBits + 7) >> 3);
@@ -120,7 +166,7 @@ float ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::d
 
 class GzHost : public Gz {
  public:
-  explicit GzHost(const cfr_gz_options &o) : block_(gz_block_bytes(o)), stride_(gz_slot_stride(block_)), threads_(o.threads) {}
+  explicit GzHost(const cfr_gz_options &o) : block_(gz_block_bytes(o)), stride_(gz_slot_stride(block_)), threads_(o.threads), dynamic_(gz_dynamic(o)) {}
 
   void compress(const uint8_t *text, uint64_t n, const uint8_t **out, uint64_t *out_n) override {
     if (!out || !out_n || (n && !text)) throw std::invalid_argument("cfr_gz_compress: null argument");
@@ -190,16 +236,17 @@ class GzHost : public Gz {
     const uint64_t n_blocks = (n + block_ - 1) / block_;
     slots_.resize(n_blocks * stride_);
     sizes_.assign(n_blocks + 1, 0);
-    std::vector<uint64_t> stored_by_thread;
+    std::vector<uint64_t> kinds_by_thread;                  // per thread: stored, fixed, dynamic
     const int threads = thread_count(n_blocks);
-    stored_by_thread.assign((size_t)threads, 0);
+    kinds_by_thread.assign((size_t)threads * 3, 0);
     parallel_slices(n_blocks, threads, [&](size_t lo, size_t hi, int tid) {
-      std::vector<uint32_t> table(1u << kGzHashBits);
+      std::vector<uint32_t> table(1u << kGzHashBits), tokens(dynamic_ ? block_ : 0);
       for (size_t b = lo; b < hi; ++b) {
         const uint64_t at = (uint64_t)b * block_;
-        bool stored;
-        sizes_[b] = encode_block(text + at, (uint32_t)std::min<uint64_t>(block_, n - at), slots_.data() + b * stride_, table, crc_table_, stored);
-        stored_by_thread[(size_t)tid] += stored ? 1 : 0;
+        uint32_t kind;
+        sizes_[b] = encode_block(text + at, (uint32_t)std::min<uint64_t>(block_, n - at), slots_.data() + b * stride_, table, crc_table_,
+                                 dynamic_ ? tokens.data() : nullptr, kind);
+        ++kinds_by_thread[(size_t)tid * 3 + kind];
       }
     });
     uint64_t total = 0;
@@ -210,13 +257,17 @@ class GzHost : public Gz {
     });
     st_.deflate_ms += ms_since(t0);
     st_.blocks += n_blocks;
-    for (uint64_t s : stored_by_thread) st_.stored_blocks += s;
+    for (int t = 0; t < threads; ++t) {
+      st_.stored_blocks += kinds_by_thread[(size_t)t * 3];
+      st_.dynamic_blocks += (uint32_t)kinds_by_thread[(size_t)t * 3 + 2];
+    }
     st_.bytes_in += n;
     st_.bytes_out += total;
   }
 
   const uint32_t block_, stride_;
   const int threads_;
+  const bool dynamic_;
   const CrcTable crc_table_;
   std::vector<uint8_t> slots_, text_, out_[kGzMaxFiles];
   std::vector<uint64_t> sizes_, off_;

@@ -27,6 +27,7 @@ class Gz {
 void gz_check_dump(const char *id_bytes, const uint64_t *id_off, const uint8_t *select, size_t n, const cfr_gz_file *files, int n_files,
                    const uint8_t *const *out, const uint64_t *out_n);
 uint32_t gz_block_bytes(const cfr_gz_options &o);      // the option checked; 0 is the default
+bool gz_dynamic(const cfr_gz_options &o);              // codes checked: 1 is dynamic mode
 
 Gz *make_gz_host(const cfr_gz_options &o);                 // cfr_gz.cpp
 Gz *make_gz_device(int device, const cfr_gz_options &o);   // cfr_gz.hip; throws HipError{.., -1} without that GPU

@@ -619,6 +619,8 @@ cfr_status cfr_last_tsv_ms(const cfr_dev_index *d, float *ms);
  * cfr_gz_open: device >= 0: the kernels of cfr_gz.hip on that GPU (CFR_ERR_NO_DEVICE without it: no fall-back); device = -1: the host
  *   twin on `threads` host threads, the same bytes.  options (NULL = defaults; a field of 0 = its default): block_bytes - the input
  *   bytes per member, 1 .. 65280 (the default, htslib's); max_blocks - at most that many workgroups per kernel.  Both exist for the tests.
+ *   codes - 0: every stream is fixed-Huffman or stored (the default); 1: dynamic mode - a member whose block is smaller with Huffman
+ *   codes of its own (BTYPE 10) gets them, every other member has the bytes of codes = 0, so no member grows; anything else: CFR_ERR_ARG.
  * cfr_gz_compress: host text in; *out points at the members, back to back, in a buffer the handle owns until its next call.  No
  *   end-of-file member.  n = 0 gives *out_n = 0.
  * cfr_gz_dump: one call makes the text of up to 4 files and compresses each; on the device the text never exists on the host.  Read i
@@ -627,11 +629,12 @@ cfr_status cfr_last_tsv_ms(const cfr_dev_index *d, float *ms);
  *   or more is left out of that file alone (what gzprintf does with it).  out / out_n: n_files entries, as for cfr_gz_compress.
  * cfr_gz_eof: the 28-byte end-of-file member, to be written once behind the last member of a file (a file of it alone is an empty text).
  * cfr_gz_get_stats: the last call: device times from events (host twin: wall times of making the text and of compressing it in
- *   format_ms and deflate_ms), summed over the files of a dump; blocks = members, stored_blocks = those that hold a stored block.
+ *   format_ms and deflate_ms), summed over the files of a dump; blocks = members, stored_blocks = those that hold a stored block,
+ *   dynamic_blocks = those that hold a dynamic block (0 with codes = 0).
  * A handle is used by one thread at a time. */
 typedef struct cfr_gz cfr_gz;
-typedef struct { int32_t block_bytes, max_blocks, threads, pad; } cfr_gz_options;
-typedef struct { float upload_ms, format_ms, deflate_ms, pack_ms, download_ms; uint32_t pad; uint64_t blocks, stored_blocks, bytes_in, bytes_out; } cfr_gz_stats;
+typedef struct { int32_t block_bytes, max_blocks, threads, codes; } cfr_gz_options;
+typedef struct { float upload_ms, format_ms, deflate_ms, pack_ms, download_ms; uint32_t dynamic_blocks; uint64_t blocks, stored_blocks, bytes_in, bytes_out; } cfr_gz_stats;
 typedef struct {
   const uint8_t *seq; const uint64_t *seq_off;      /* n + 1 offsets */
   const char *qual; const uint64_t *qual_off;       /* NULL, or n + 1 offsets */

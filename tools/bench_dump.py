@@ -14,6 +14,10 @@ binned to few quality values looks like); every read selected, one file.
   --cli FILE   bin/centrifuger -u FILE --un A --cl B -t 16 end to end, index --cli-index, with and without --gpu-dump, --cli-runs
            alternating runs each: every run's wall time, the md5 of its TSV, the size of its dump files, the md5 of what they inflate
            to (first run only) and the stages' busy seconds (CFR_CLI_TIMING) appended to profiles/gpu_dump_cli_timing.txt.
+  --codes dynamic   the same two parts for dynamic Huffman codes (cfr_gz_options.codes = 1, --gpu-dump-codes dynamic) beside the fixed code:
+           --api runs a fixed and a dynamic device handle in one process, their calls alternating, and reports both kernels' event
+           times, both sizes and the sizes against zlib level 1 under the key "api_dynamic"; --cli runs --gpu-dump with the fixed code
+           and with dynamic codes alternately, under "cli_dynamic".  The keys of the default --codes fixed stay as they are.
 Every part merges its figures into the JSON file given by --out."""
 import argparse
 import hashlib
@@ -131,10 +135,71 @@ def part_api(n, reps):
     return rows
 
 
-def part_cli(reads_file, index, runs, log):
+def part_api_dynamic(n, reps):
+    """a fixed and a dynamic device handle over the same arrays, their calls alternating; the dynamic host twin for the bytes; zlib level 1"""
+    from centrifuger_amd import capi
+    idb, ido = make_ids(n)
+    seq, so, qual, qo = make_reads(n)
+    say("reads made")
+    select, has = np.ones(n, dtype=np.uint8), np.ones(n, dtype=np.uint8)
+    files = [(seq, so, qual, qo, has)]
+    rows = {"reads": n, "read_len": 150, "id_bytes": 20}
+    handles = {"fixed": capi.Gz(device=0), "dynamic": capi.Gz(device=0, codes="dynamic")}
+    ms = {name: {k: [] for k in ("format_ms", "deflate_ms", "pack_ms", "download_ms", "wall_ms")} for name in handles}
+    md5, text = {}, None
+    for r in range(reps + 1):
+        for name, h in handles.items():
+            t = time.perf_counter()
+            if r == 0:
+                members = h.dump_arrays(idb, ido, select, files)[0]
+                md5[name] = hashlib.md5(members).hexdigest()
+                got = inflate_members(members)
+                assert text is None or got == text
+                text = got
+                del members, got
+                continue
+            h.dump_arrays(idb, ido, select, files, copy=False)
+            w = (time.perf_counter() - t) * 1e3
+            st = h.stats()
+            for k in ms[name]:
+                ms[name][k].append(w if k == "wall_ms" else getattr(st, k))
+    for name, h in handles.items():
+        st = h.stats()
+        row = {k: statistics.median(v) for k, v in ms[name].items()}
+        row["deflate_ms_all"] = ms[name]["deflate_ms"]
+        row["md5"] = md5[name]
+        row["blocks"], row["stored_blocks"], row["dynamic_blocks"], row["bytes_in"], row["bytes_out"] = (int(st.blocks), int(st.stored_blocks), int(st.dynamic_blocks),
+                                                                                                         int(st.bytes_in), int(st.bytes_out))
+        row["gb_per_s_deflate_kernel"] = st.bytes_in / row["deflate_ms"] / 1e6
+        rows[name] = row
+        h.close()
+        say(name, json.dumps(row))
+    host = capi.Gz(threads=16, codes="dynamic")
+    t = time.perf_counter()
+    members = host.dump_arrays(idb, ido, select, files)[0]
+    rows["host_16_threads_dynamic"] = {"wall_ms": (time.perf_counter() - t) * 1e3, "deflate_ms": host.stats().deflate_ms, "md5": hashlib.md5(members).hexdigest()}
+    assert rows["host_16_threads_dynamic"]["md5"] == md5["dynamic"]
+    del members
+    host.close()
+    rows["text_bytes"] = len(text)
+    say("zlib level 1 over", len(text), "bytes")
+    t = time.perf_counter()
+    z = zlib.compress(text, 1)
+    w = time.perf_counter() - t
+    rows["zlib_level_1_one_thread"] = {"seconds": w, "gb_per_s": len(text) / w / 1e9, "compressed_bytes": len(z)}
+    rows["size_against_zlib_level_1"] = {k: rows[k]["bytes_out"] / len(z) for k in handles}
+    rows["size_dynamic_against_fixed"] = rows["dynamic"]["bytes_out"] / rows["fixed"]["bytes_out"]
+    rows["deflate_time_dynamic_against_fixed"] = rows["dynamic"]["deflate_ms"] / rows["fixed"]["deflate_ms"]
+    rows["ratio"] = {"fixed_huffman_bgzf": len(text) / rows["fixed"]["bytes_out"], "dynamic_huffman_bgzf": len(text) / rows["dynamic"]["bytes_out"], "zlib_level_1": len(text) / len(z)}
+    return rows
+
+
+def part_cli(reads_file, index, runs, log, dynamic=False):
     cli = os.path.join(BIN, "centrifuger")
     env = dict(os.environ, CFR_CLI_TIMING="1")
     variants = {"host_dump": [], "gpu_dump": ["--gpu-dump"]}
+    if dynamic:
+        variants = {"gpu_dump": ["--gpu-dump"], "gpu_dump_dynamic": ["--gpu-dump", "--gpu-dump-codes", "dynamic"]}
     out = {k: {"seconds": [], "md5": [], "dump_bytes": []} for k in variants}
     with open(log, "a") as lf:
         lf.write(f"# -u {reads_file} --un A --cl B  index {index}  -t 16  ({time.strftime('%Y-%m-%d %H:%M:%S')})\n")
@@ -149,7 +214,7 @@ def part_cli(reads_file, index, runs, log):
                 sizes = {f: os.path.getsize(os.path.join(work, f)) for f in sorted(os.listdir(work))}
                 out[name]["seconds"].append(round(w, 3)); out[name]["md5"].append(md5); out[name]["dump_bytes"].append(sizes)
                 clocks = " ".join("%s %s" % tuple(l.split()[1:3]) for l in p.stderr.decode().splitlines() if l.startswith("[timing]"))
-                lf.write(f"run {r} {name:10s} {w:8.3f} s  md5 {md5}  dumps {sizes}  busy s: {clocks}\n")
+                lf.write(f"run {r} {name:{16 if dynamic else 10}s} {w:8.3f} s  md5 {md5}  dumps {sizes}  busy s: {clocks}\n")
                 lf.flush()
                 say(f"run {r} {name} {w:.3f} s")
                 if r == 0:                                      # what the dumps inflate to: gzip reads both framings
@@ -161,10 +226,11 @@ def part_cli(reads_file, index, runs, log):
                         assert z.wait() == 0
                         inflated[f] = h.hexdigest()
                     out[name]["inflated_md5"] = inflated
-                    lf.write(f"run {r} {name:10s} inflated md5 {inflated}\n")
+                    lf.write(f"run {r} {name:{16 if dynamic else 10}s} inflated md5 {inflated}\n")
                     lf.flush()
                 shutil.rmtree(work)
-    assert out["host_dump"]["inflated_md5"] == out["gpu_dump"]["inflated_md5"] and set(out["host_dump"]["md5"]) == set(out["gpu_dump"]["md5"])
+    first, second = list(variants)
+    assert out[first]["inflated_md5"] == out[second]["inflated_md5"] and set(out[first]["md5"]) == set(out[second]["md5"])
     for v in out.values():
         v["median_seconds"] = statistics.median(v["seconds"])
     return out
@@ -180,6 +246,7 @@ def main():
     ap.add_argument("--cli-index")
     ap.add_argument("--cli-runs", type=int, default=4)
     ap.add_argument("--cli-log", default=os.path.join(ROOT, "profiles", "gpu_dump_cli_timing.txt"))
+    ap.add_argument("--codes", choices=("fixed", "dynamic"), default="fixed")
     a = ap.parse_args()
     doc = json.load(open(a.out)) if os.path.exists(a.out) else {}
 
@@ -187,13 +254,17 @@ def main():
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(doc, f, indent=1, sort_keys=True)
+    dynamic = a.codes == "dynamic"
     if a.api:
-        doc["api"] = part_api(a.reads, a.reps)
+        if dynamic:
+            doc["api_dynamic"] = part_api_dynamic(a.reads, a.reps)
+        else:
+            doc["api"] = part_api(a.reads, a.reps)
         save()
     if a.cli:
         if not a.cli_index:
             ap.error("--cli needs --cli-index")
-        doc.setdefault("cli", {})[os.path.basename(a.cli)] = part_cli(a.cli, a.cli_index, a.cli_runs, a.cli_log)
+        doc.setdefault("cli_dynamic" if dynamic else "cli", {})[os.path.basename(a.cli)] = part_cli(a.cli, a.cli_index, a.cli_runs, a.cli_log, dynamic)
         save()
     print(json.dumps(doc, sort_keys=True))
 

@@ -8,6 +8,7 @@
 // Every input goes into a heap block of exactly its size - so a read one byte off is a report - and is compressed with 1 and with 3
 // threads: both must give the same bytes, and the members are undone here (stored blocks copied, fixed-Huffman blocks decoded by a
 // small inflater of this file's own) and compared with the text.
+//   ./gz_sanitize corpus.bin dynamic   the same items with cfr_gz_options.codes = 1; the inflater reads dynamic blocks (BTYPE 10) too.
 // Exit status 0: no report, every text came back.
 #include <cstdio>
 #include <cstdlib>
@@ -42,30 +43,83 @@ struct Bits {
   uint32_t high_first(int n) { uint32_t v = 0; for (int i = 0; i < n; ++i) v = (v << 1) | (uint32_t)bit(); return v; }
 };
 
-static void inflate_fixed(Bits &in, std::string &out) {
+// a Huffman code from its lengths (RFC 1951, 3.2.2), decoded bit by bit
+struct Code {
+  uint16_t count[16] = {0}, symbol[288] = {0};
+  Code(const uint8_t *len, int n) {
+    for (int s = 0; s < n; ++s) ++count[len[s]];
+    count[0] = 0;
+    uint16_t offs[16] = {0};
+    for (int l = 1; l < 15; ++l) offs[l + 1] = (uint16_t)(offs[l] + count[l]);
+    for (int s = 0; s < n; ++s) if (len[s]) symbol[offs[len[s]]++] = (uint16_t)s;
+  }
+  uint32_t decode(Bits &in) const {
+    int code = 0, first = 0, index = 0;
+    for (int l = 1; l <= 15; ++l) {
+      code |= in.bit();
+      const int c = count[l];
+      if (code - c < first) return symbol[index + (code - first)];
+      index += c; first += c; first <<= 1; code <<= 1;
+    }
+    throw std::runtime_error("a code that no symbol has");
+  }
+};
+
+// lit == nullptr: the fixed code
+static void inflate_codes(Bits &in, std::string &out, const Code *lit, const Code *dist);
+static void inflate_fixed(Bits &in, std::string &out) { inflate_codes(in, out, nullptr, nullptr); }
+
+static void inflate_dynamic(Bits &in, std::string &out) {
+  static const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+  const uint32_t hlit = in.low_first(5) + 257, hdist = in.low_first(5) + 1, hclen = in.low_first(4) + 4;
+  if (hlit > 286 || hdist > 30) throw std::runtime_error("HLIT / HDIST out of range");
+  uint8_t cl[19] = {0}, len[286 + 30] = {0};
+  for (uint32_t i = 0; i < hclen; ++i) cl[order[i]] = (uint8_t)in.low_first(3);
+  const Code clc(cl, 19);
+  for (uint32_t i = 0; i < hlit + hdist;) {
+    const uint32_t sym = clc.decode(in);
+    if (sym < 16) { len[i++] = (uint8_t)sym; continue; }
+    uint32_t rep;
+    uint8_t v = 0;
+    if (sym == 16) { if (!i) throw std::runtime_error("a repeat with nothing in front"); v = len[i - 1]; rep = 3 + in.low_first(2); }
+    else if (sym == 17) rep = 3 + in.low_first(3);
+    else rep = 11 + in.low_first(7);
+    if (i + rep > hlit + hdist) throw std::runtime_error("a repeat runs over the end of the lengths");
+    while (rep--) len[i++] = v;
+  }
+  if (!len[256]) throw std::runtime_error("no end-of-block code");
+  const Code lit(len, (int)hlit), dist(len + hlit, (int)hdist);
+  inflate_codes(in, out, &lit, &dist);
+}
+
+static void inflate_codes(Bits &in, std::string &out, const Code *lit, const Code *dist) {
   static const uint16_t len_base[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
   static const uint8_t len_extra[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
   static const uint16_t dist_base[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
   static const uint8_t dist_extra[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
   const size_t first = out.size();
   for (;;) {
-    uint32_t code = in.high_first(7), sym;
-    if (code <= 0x17) sym = 256 + code;
+    uint32_t sym;
+    if (lit) sym = lit->decode(in);
     else {
-      code = (code << 1) | (uint32_t)in.bit();
-      if (code >= 0x30 && code <= 0xbf) sym = code - 0x30;
-      else if (code >= 0xc0 && code <= 0xc7) sym = 280 + (code - 0xc0);
-      else { code = (code << 1) | (uint32_t)in.bit(); sym = 144 + (code - 0x190); }
+      uint32_t code = in.high_first(7);
+      if (code <= 0x17) sym = 256 + code;
+      else {
+        code = (code << 1) | (uint32_t)in.bit();
+        if (code >= 0x30 && code <= 0xbf) sym = code - 0x30;
+        else if (code >= 0xc0 && code <= 0xc7) sym = 280 + (code - 0xc0);
+        else { code = (code << 1) | (uint32_t)in.bit(); sym = 144 + (code - 0x190); }
+      }
     }
     if (sym < 256) { out.push_back((char)sym); continue; }
     if (sym == 256) return;
     if (sym > 285) throw std::runtime_error("a length symbol above 285");
     const uint32_t len = len_base[sym - 257] + in.low_first(len_extra[sym - 257]);
-    const uint32_t dc = in.high_first(5);
+    const uint32_t dc = dist ? dist->decode(in) : in.high_first(5);
     if (dc > 29) throw std::runtime_error("a distance code above 29");
-    const uint32_t dist = dist_base[dc] + in.low_first(dist_extra[dc]);
-    if (dist > out.size() - first) throw std::runtime_error("a distance that reaches in front of the block");
-    for (uint32_t k = 0; k < len; ++k) out.push_back(out[out.size() - dist]);
+    const uint32_t distance = dist_base[dc] + in.low_first(dist_extra[dc]);
+    if (distance > out.size() - first) throw std::runtime_error("a distance that reaches in front of the block");
+    for (uint32_t k = 0; k < len; ++k) out.push_back(out[out.size() - distance]);
   }
 }
 
@@ -75,6 +129,9 @@ static uint32_t crc32_of(const char *p, size_t n) {
   for (size_t i = 0; i < n; ++i) c = cfr::gz_crc_byte(table, c, (uint8_t)p[i]);
   return c ^ 0xffffffffu;
 }
+
+static bool g_dynamic = false;             // argv[2] == "dynamic": codes = 1, and BTYPE 10 is expected
+static size_t g_dynamic_members = 0;
 
 static std::string undo(const uint8_t *m, uint64_t n, uint32_t block_bytes) {
   std::string out;
@@ -92,8 +149,8 @@ static std::string undo(const uint8_t *m, uint64_t n, uint32_t block_bytes) {
       const uint32_t len = (uint32_t)(s[0] | (s[1] << 8));
       if ((uint32_t)(s[2] | (s[3] << 8)) != (~len & 0xffffu) || 23 + len + 8 != size) throw std::runtime_error("a bad stored block");
       out.append((const char *)s + 4, len);
-    } else if (type == 1) {
-      inflate_fixed(in, out);
+    } else if (type == 1 || (type == 2 && g_dynamic)) {
+      if (type == 1) inflate_fixed(in, out); else { inflate_dynamic(in, out); ++g_dynamic_members; }
       if (in.p + (in.at ? 1 : 0) != in.end) throw std::runtime_error("bytes between the stream and the trailer");
     } else throw std::runtime_error("a block type the twin does not write");
     const uint8_t *t = m + at + size - 8;
@@ -106,7 +163,8 @@ static std::string undo(const uint8_t *m, uint64_t n, uint32_t block_bytes) {
 }
 
 int main(int argc, char **argv) {
-  if (argc != 2) { fprintf(stderr, "usage: %s corpus.bin\n", argv[0]); return 2; }
+  if (argc != 2 && !(argc == 3 && !strcmp(argv[2], "dynamic"))) { fprintf(stderr, "usage: %s corpus.bin [dynamic]\n", argv[0]); return 2; }
+  g_dynamic = argc == 3;
   FILE *f = fopen(argv[1], "rb");
   if (!f) { perror(argv[1]); return 2; }
   size_t n_items = 0;
@@ -117,6 +175,7 @@ int main(int argc, char **argv) {
       if (!get(f, &bb, 4) || !get(f, &n, 8)) throw std::runtime_error("short corpus file");
       cfr_gz_options o{};
       o.block_bytes = (int32_t)bb;
+      o.codes = g_dynamic ? 1 : 0;
       std::unique_ptr<cfr::Gz> g[2];
       o.threads = 1; g[0].reset(cfr::make_gz_host(o));
       o.threads = 3; g[1].reset(cfr::make_gz_host(o));
@@ -176,6 +235,7 @@ int main(int argc, char **argv) {
     return 1;
   }
   fclose(f);
+  if (g_dynamic) printf("gz_sanitize: %zu members with dynamic codes\n", g_dynamic_members);
   printf("gz_sanitize: %zu items, every text came back\n", n_items);
   return 0;
 }
