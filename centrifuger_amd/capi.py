@@ -102,6 +102,7 @@ EXPORTS = [
     "cfr_barcode_destroy", "cfr_barcode_translate_open", "cfr_barcode_translate_apply", "cfr_barcode_translate_destroy",
     "cfr_tsv_header_ex", "cfr_format_tsv_ex",
     "cfr_taxonomy_open", "cfr_taxonomy_get_tables", "cfr_taxonomy_tax_name", "cfr_taxonomy_seq_name", "cfr_tax_rank_string", "cfr_taxonomy_close",
+    "cfr_taxonomy_lca_probe",
     "cfr_promote_open", "cfr_promote_apply", "cfr_promote_lca_warnings", "cfr_promote_get_stats", "cfr_promote_close",
     "cfr_device_index_set_promote", "cfr_last_promote_ms",
     "cfr_kreport_options_default", "cfr_kreport_open", "cfr_kreport_add_results", "cfr_kreport_add_tsv", "cfr_kreport_add_count_table",
@@ -903,6 +904,17 @@ class Taxonomy:
 
     def tax_name(self, ctid: int) -> str:
         return lib().cfr_taxonomy_tax_name(self._t, C.c_uint64(ctid)).decode()
+
+    def lca(self, lists, fold=False):
+        """Taxonomy::LCA of every list of compact tax ids: the host tail's restatement, or (fold) the fold the kernels use -> (results,
+        the fold's loop iterations per list)"""
+        begin = np.zeros(len(lists) + 1, dtype=np.uint64)
+        begin[1:] = np.cumsum([len(x) for x in lists])
+        ids = _u64(np.array([t for x in lists for t in x], dtype=np.uint64))
+        out = np.zeros(len(lists), dtype=np.uint64)
+        steps = np.zeros(len(lists), dtype=np.uint32)
+        _check(lib().cfr_taxonomy_lca_probe(self._t, _p(ids), _p(begin), C.c_size_t(len(lists)), C.c_int32(1 if fold else 0), _p(out), _p(steps)))
+        return out, steps
 
     def close(self):
         if self._t:

@@ -209,12 +209,12 @@ void write_taxonomy(const std::string &path, const BuildInput &in) {
   for (uint64_t tid : present) {
     uint64_t p = tid;
     if (!tree.count(p)) continue;
+    // ReadTaxonomyTree walks with std::map operator[] (Taxonomy.hpp:190-197): a parent the file does not name is default-constructed
+    // on the way - parent 0, rank code 0, no leaf - and so is tax id 0 after it, which is its own parent.  Both phantom nodes are kept
+    // (and a later id of `present` finds them in the tree), so an orphaned subtree gives a forest whose first top is the phantom id 0.
     while (!selected.count(p)) {
       selected.insert(p);
-      auto it = tree.find(p);
-      if (it == tree.end()) break;
-      p = it->second.first;
-      if (!tree.count(p)) break;
+      p = tree[p].first;
     }
   }
   std::vector<uint64_t> order(selected.begin(), selected.end());  // compact ids follow ascending original id (std::map order)

@@ -773,6 +773,25 @@ const char *cfr_taxonomy_seq_name(const cfr_taxonomy *t, uint64_t seq_id) {
 const char *cfr_tax_rank_string(uint8_t rank) { return cfr::quant_rank_string(rank); }
 void cfr_taxonomy_close(cfr_taxonomy *t) { delete t; }
 
+cfr_status cfr_taxonomy_lca_probe(const cfr_taxonomy *t, const uint64_t *ids, const uint64_t *begin, size_t n_lists, int32_t form,
+                                  uint64_t *out, uint32_t *steps) {
+  if (!t || !begin || !out || (n_lists && begin[n_lists] && !ids)) return bad_arg("cfr_taxonomy_lca_probe: null argument");
+  if (form != 0 && form != 1) return bad_arg("cfr_taxonomy_lca_probe: form is 0 or 1");
+  return guarded([&]() -> cfr_status {
+    for (size_t i = 0; i < n_lists; ++i) if (begin[i] > begin[i + 1]) throw std::invalid_argument("cfr_taxonomy_lca_probe: begin must ascend");
+    for (uint64_t j = 0; j < begin[n_lists]; ++j) if (ids[j] >= t->tax.node_cnt) throw std::invalid_argument("cfr_taxonomy_lca_probe: id outside the tree");
+    const std::vector<uint32_t> depth = cfr::promote_depths(t->tax.parent);
+    std::vector<uint64_t> one;
+    for (size_t i = 0; i < n_lists; ++i) {
+      uint32_t st = 0;
+      if (form == 0) { one.assign(ids + begin[i], ids + begin[i + 1]); out[i] = cfr::tax_lca(t->tax, one); }
+      else out[i] = cfr::tax_lca_fold(t->tax, depth, ids + begin[i], (size_t)(begin[i + 1] - begin[i]), &st);
+      if (steps) steps[i] = st;
+    }
+    return CFR_OK;
+  });
+}
+
 // ---- centrifuger-promote ----
 cfr_status cfr_promote_open(const char *idx_prefix, const char *level, int device, cfr_promote **out) {
   if (!idx_prefix || !level || !out) return bad_arg("cfr_promote_open: null argument");

@@ -40,6 +40,7 @@
 #include "cfr_index.hpp"
 #include "cfr_kreport_core.hpp"
 #include "cfr_promote_core.hpp"
+#include "cfr_tax_fold.hpp"
 #include "cfr_tsv_core.hpp"
 
 namespace cfr {

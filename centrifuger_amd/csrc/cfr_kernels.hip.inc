@@ -1614,22 +1614,11 @@ __device__ __forceinline__ uint64_t unique_u64(uint64_t *a, uint64_t m) {
   return w;
 }
 
-// lowest common ancestor of the non-root ids (root if all are root): same value as Taxonomy::LCA
+// lowest common ancestor of the ids, in their order (root if all are root): same value as Taxonomy::LCA
 __device__ __forceinline__ uint64_t d_tax_lca(const DevView &v, const uint64_t *ids, uint64_t cnt) {
-  auto depth = [&](uint64_t x) { return v.tax_depth[x]; };   // steps to the root, tabulated at load time
-  uint64_t cur = v.tax_root;
-  uint32_t dcur = 0;
-  bool have = false;
-  for (uint64_t i = 0; i < cnt; ++i) {
-    uint64_t x = ids[i];
-    if (x == v.tax_parent[x]) continue;            // a root id is ignored
-    uint32_t dx = depth(x);
-    if (!have) { cur = x; dcur = dx; have = true; continue; }
-    while (dx > dcur) { x = v.tax_parent[x]; --dx; }
-    while (dcur > dx) { cur = v.tax_parent[cur]; --dcur; }
-    while (cur != x) { cur = v.tax_parent[cur]; x = v.tax_parent[x]; --dcur; }
-  }
-  return have ? cur : v.tax_root;
+  TaxFold F = tax_fold_begin(v.tax_root);              // (cfr_tax_fold.hpp: the rules on a forest; tax_depth is tabulated at load time)
+  for (uint64_t i = 0; i < cnt; ++i) tax_fold_add(v.tax_parent, v.tax_depth, v.tax_root, F, ids[i]);
+  return tax_fold_result(F, v.tax_root);
 }
 
 // the node the reference's walk files under rank level L for input id (or ~0 if none)
@@ -1701,6 +1690,12 @@ __device__ __forceinline__ void d_tax_expand(const DevView &v, uint64_t *ids, ui
     // of the LCA on the way to every non-root id that is not the LCA itself (ids that part further down share the backbone's child)
     const uint64_t lca = promoted[0];
     uint64_t m = 0;
+    // a second top as the backbone (the first id that is not the root, cfr_tax_fold.hpp) is the backbone's own node below the root (:770)
+    for (uint64_t i = 0; i < cnt; ++i) {
+      if (ids[i] == v.tax_root) continue;
+      if (ids[i] == v.tax_parent[ids[i]] && ids[i] != lca) tmp[m++] = ids[i];
+      break;
+    }
     for (uint64_t i = 0; i < cnt; ++i) {
       uint64_t x = ids[i];
       if (x == v.tax_parent[x] || x == lca) continue;            // a root id takes no part (:787-791); the LCA itself leaves nothing (iTmp < 0)
@@ -2142,24 +2137,15 @@ __device__ __forceinline__ bool tail_emit_small(const DevView &v, const uint64_t
   }
   if (v.max_result != 1 || v.exp_pool) return false;          // (--expand-taxid: the general form keeps the promoted ids)
   // ReduceTaxIds with k = 1 (Taxonomy.hpp:839-973): an id outside the tree gives the node count, otherwise the LCA
-  uint64_t cur = v.tax_root;
-  uint32_t dcur = 0;
-  bool have = false, outside = false;
+  TaxFold L = tax_fold_begin(v.tax_root);                 // (cfr_tax_fold.hpp: bid is in the reference's order)
+  bool outside = false;
 #pragma unroll
   for (int q = 0; q < 8; ++q) if ((uint32_t)q < nb) {
-    uint64_t x = d_seq_to_tax(v, bid[q]);
+    const uint64_t x = d_seq_to_tax(v, bid[q]);
     if (x >= v.node_cnt) outside = true;
-    else if (x != v.tax_parent[x]) {                      // (a root id is ignored, like Taxonomy::LCA)
-      uint32_t dx = v.tax_depth[x];
-      if (!have) { cur = x; dcur = dx; have = true; }
-      else {
-        while (dx > dcur) { x = v.tax_parent[x]; --dx; }
-        while (dcur > dx) { cur = v.tax_parent[cur]; --dcur; }
-        while (cur != x) { cur = v.tax_parent[cur]; x = v.tax_parent[x]; --dcur; }
-      }
-    }
+    else tax_fold_add(v.tax_parent, v.tax_depth, v.tax_root, L, x);
   }
-  const uint64_t out = outside ? v.node_cnt : (have ? cur : v.tax_root);
+  const uint64_t out = outside ? v.node_cnt : tax_fold_result(L, v.tax_root);
   cfr_match m;
   m.id = out; m.taxid = d_orig_taxid(v, out); m.kind = 1; m.pad = 0;
   M[0] = m;
@@ -2538,24 +2524,15 @@ __global__ __launch_bounds__(256, 5) void k_post_fast(DevView v, const uint64_t 
         results[i] = R;
       } else if (v.max_result == 1 && !v.exp_pool) {
         // ReduceTaxIds with k = 1 (Taxonomy.hpp:839-973): an id outside the tree gives the node count, otherwise the LCA (tail_emit_small)
-        uint64_t cur = v.tax_root;
-        uint32_t dcur = 0;
-        bool have = false, outside = false;
+        TaxFold F = tax_fold_begin(v.tax_root);                 // (cfr_tax_fold.hpp: bid is in the reference's order)
+        bool outside = false;
 #pragma unroll
         for (int q = 0; q < 8; ++q) if ((uint32_t)q < nb) {
-          uint64_t x = d_seq_to_tax(v, bid[q]);
+          const uint64_t x = d_seq_to_tax(v, bid[q]);
           if (x >= v.node_cnt) outside = true;
-          else if (x != v.tax_parent[x]) {                      // (a root id is ignored, like Taxonomy::LCA)
-            uint32_t dx = v.tax_depth[x];
-            if (!have) { cur = x; dcur = dx; have = true; }
-            else {
-              while (dx > dcur) { x = v.tax_parent[x]; --dx; }
-              while (dcur > dx) { cur = v.tax_parent[cur]; --dcur; }
-              while (cur != x) { cur = v.tax_parent[cur]; x = v.tax_parent[x]; --dcur; }
-            }
-          }
+          else tax_fold_add(v.tax_parent, v.tax_depth, v.tax_root, F, x);
         }
-        const uint64_t out = outside ? v.node_cnt : (have ? cur : v.tax_root);
+        const uint64_t out = outside ? v.node_cnt : tax_fold_result(F, v.tax_root);
         cfr_match m;
         m.id = out; m.taxid = d_orig_taxid(v, out); m.kind = 1; m.pad = 0;
         M[0] = m;
@@ -2881,36 +2858,46 @@ __global__ __launch_bounds__(TEAM * TPB) void k_tail_heavy(DevView v, const uint
         }
         R.n_match = (int32_t)nb;
       } else if (v.max_result == 1 && !v.exp_pool) {            // (--expand-taxid: the single-lane form keeps the promoted ids)
-        // ReduceTaxIds with k = 1 (Taxonomy.hpp:839-973): an id outside the tree gives the node count, otherwise the LCA of
-        // the non-root ids - a set function, folded per lane and then pairwise across the team
-        uint64_t cur = v.tax_root;
-        uint32_t dcur = 0;
-        bool have = false, outside = false;
-        auto join = [&](uint64_t x, uint32_t dx) {
-          if (!have) { cur = x; dcur = dx; have = true; return; }
-          while (dx > dcur) { x = v.tax_parent[x]; --dx; }
-          while (dcur > dx) { cur = v.tax_parent[cur]; --dcur; }
-          while (cur != x) { cur = v.tax_parent[cur]; x = v.tax_parent[x]; --dcur; }
-        };
+        // ReduceTaxIds with k = 1 (Taxonomy.hpp:839-973): an id outside the tree gives the node count, otherwise Taxonomy::LCA.  On a
+        // forest that is no set function of the ids (cfr_tax_fold.hpp): the first id that is not the root is the backbone even when
+        // it is the top of a second tree.  The ids that are no top ARE folded as a set, per lane and then across the team; `first`
+        // is the first non-root id in the reference's order (class, strand list, id), with bit 0 clear when that id is a top.
+        TaxFold F = tax_fold_begin(v.tax_root);
+        bool outside = false;
+        uint64_t first = ~0ull, first_x = v.tax_root;
         for (uint32_t q = tl; q < nb; q += kTeam) {
-          const uint64_t x = d_seq_to_tax(v, (uint64_t)(tab[list[q]].key & 0x7fffffffu));
+          const TeamSlot e = tab[list[q]];
+          const uint64_t x = d_seq_to_tax(v, (uint64_t)(e.key & 0x7fffffffu));
           if (x >= v.node_cnt) outside = true;
-          else if (x != v.tax_parent[x]) join(x, v.tax_depth[x]);               // (a root id is ignored, like Taxonomy::LCA)
+          else if (x != v.tax_root) {
+            const bool top = x == v.tax_parent[x];
+            const uint64_t ord = ((((uint64_t)cls(e.score) << 32) | (uint64_t)e.key) << 1) | (top ? 0ull : 1ull);
+            if (ord < first) { first = ord; first_x = x; }
+            if (!top) tax_fold_add(v.tax_parent, v.tax_depth, v.tax_root, F, x);
+          }
         }
         // across the team: everybody up to the smallest depth, then level by level until all stand on one node (one
         // round of loads per level instead of a pairwise climb per butterfly step)
+        uint64_t cur = F.cur;
+        uint32_t dcur = F.dcur;
+        bool have = F.have;
         uint32_t dmin = have ? dcur : ~0u;
         uint64_t any = ((uint64_t)have) | ((uint64_t)outside << 1);
         for (int m = kTeam / 2; m > 0; m >>= 1) {
           const uint64_t o = team_shfl_xor((uint64_t)dmin | (any << 32), m);
           if ((uint32_t)o < dmin) dmin = (uint32_t)o;
           any |= o >> 32;
+          const uint64_t of = team_shfl_xor(first, m), ox = team_shfl_xor(first_x, m);
+          if (of < first) { first = of; first_x = ox; }
         }
         outside = (any >> 1) & 1ull;
         const bool team_have = any & 1ull;
         if (team_have && !outside) {
           if (have) while (dcur > dmin) { cur = v.tax_parent[cur]; --dcur; }
           for (;;) {
+            // depth 0: the lanes stand on the tops of their trees (or all on a second top): every path ends in the root.  dmin
+            // is the same in every lane and counts down, so the climb ends on any forest
+            if (dmin == 0) { cur = v.tax_root; break; }
             // the smallest node anybody stands on, and whether anybody stands elsewhere
             uint64_t ref = have ? cur : ~0ull;
             for (int m = kTeam / 2; m > 0; m >>= 1) { const uint64_t o = team_shfl_xor(ref, m); if (o < ref) ref = o; }
@@ -2918,9 +2905,11 @@ __global__ __launch_bounds__(TEAM * TPB) void k_tail_heavy(DevView v, const uint
             for (int m = kTeam / 2; m > 0; m >>= 1) differ |= team_shfl_xor(differ, m);
             if (!differ) { cur = ref; break; }
             if (have) cur = v.tax_parent[cur];
+            --dmin;
           }
+          if (!(first & 1ull)) cur = v.tax_root;              // the backbone is a second top, and some id is none: the root
           have = true;
-        }
+        } else if (!outside && first != ~0ull) { cur = first_x; have = true; }   // tops only: the first that is not the root
         const uint64_t out = outside ? v.node_cnt : (have ? cur : v.tax_root);
         if (tl == 0) {
           cfr_match m;

@@ -444,7 +444,13 @@ void Quant::finish_coalesce() {
 
 const QuantAssignments &Quant::assignments() { finish_coalesce(); return assign_; }
 
-// Taxonomy::ConvertToGeneralTree (Taxonomy.hpp:1086-1108), the second loop included as it stands
+// Taxonomy::ConvertToGeneralTree (Taxonomy.hpp:1086-1108).  Its second loop is there to "connect the disjoint trees to the root".
+// One deliberate difference, which shows on a forest only: the reference's loop also meets the root itself (its parent field is the
+// root and it is no child of its own) and adds the edge root -> root; Tree_Plain uses the root's index as its "no child" mark, so the
+// next top that is added finds "no child yet" and REPLACES the root's child list - the root then counts the second tree alone (107.3
+// of 210 reads in tests/tax_worlds.py's orphan_subtree).  Here the root is left out of that loop, so every top hangs below the root
+// beside the root's own children, which is what the loop's comment says it is for.  On a single-rooted taxonomy nothing changes (the
+// self-edge ends up behind the last child, where the children walk stops anyway): the reports stay the reference's byte for byte.
 void Quant::general_tree(PlainTree &tree) const {
   const size_t nc = tax_.node_cnt;
   tree.init(nc, tax_.root);
@@ -452,7 +458,7 @@ void Quant::general_tree(PlainTree &tree) const {
   std::vector<size_t> rc = tree.children(tree.root);
   std::vector<char> is_root_child(nc, 0);
   for (size_t c : rc) is_root_child[c] = 1;
-  for (size_t i = 0; i < nc; ++i) if (tree.nodes[i].parent == tree.root && !is_root_child[i]) tree.add_edge(i, tree.root);
+  for (size_t i = 0; i < nc; ++i) if (i != tree.root && tree.nodes[i].parent == tree.root && !is_root_child[i]) tree.add_edge(i, tree.root);
 }
 
 int Quant::run() {
@@ -496,7 +502,12 @@ int Quant::run() {
   const size_t ns = inverse.size();
   PlainTree sub;
   sub.init(ns, 0);
-  for (size_t i = 1; i < ns; ++i) sub.add_edge(i, to_sub[tax_.parent[inverse[i]]]);
+  // (a covered top other than the root hangs below the root here too, as in general_tree: with the taxonomy's own parent it would be
+  //  its own child and the EM's tree passes, which start at the root, would never see its tree)
+  for (size_t i = 1; i < ns; ++i) {
+    const uint64_t par = tax_.parent[inverse[i]];
+    sub.add_edge(i, par == inverse[i] ? 0 : to_sub[par]);
+  }
   Tree ch(ns);
   for (size_t i = 0; i < ns; ++i) ch[i] = sub.children(i);
   std::vector<uint64_t> len(ns, 0);

@@ -5,6 +5,7 @@
 // taxonomy side-table logic it calls: Taxonomy::SeqIdToTaxId / GetOrigTaxId / LCA / ReduceTaxIds
 // (Taxonomy.hpp:718-724, 633-639, 733-836, 839-973).  Pure host integer work, threaded over reads.
 #include "cfr_tail.hpp"
+#include "cfr_tax_fold.hpp"
 #include "cfr_threads.hpp"
 
 #include <algorithm>
@@ -70,12 +71,24 @@ uint64_t tax_lca(const Taxonomy &t, const std::vector<uint64_t> &ids) {
   return t.root;
 }
 
+uint64_t tax_lca_fold(const Taxonomy &t, const std::vector<uint32_t> &depth, const uint64_t *ids, size_t cnt, uint32_t *steps) {
+  TaxFold F = tax_fold_begin(t.root);
+  for (size_t i = 0; i < cnt; ++i) tax_fold_add(t.parent.data(), depth.data(), t.root, F, ids[i], steps);
+  return tax_fold_result(F, t.root);
+}
+
 // lcaChildTaxIds of Taxonomy::LCA (Taxonomy.hpp:771-777, 806-813, 822-830) for its result `lca`: the reference keeps one ordered set per
 // node of the first id's lineage - the lineage's own node below it, and for every other id the node at which its path leaves the
 // lineage - and hands back the set of the LCA's place.  An id whose path leaves further down shares the lineage's node below the
 // LCA, the LCA itself and root ids leave nothing: so the set is { child of lca on the way down to x : x in ids, x not a root, x != lca }.
 void tax_lca_children(const Taxonomy &t, const std::vector<uint64_t> &ids, uint64_t lca, std::vector<uint64_t> &children) {
   children.clear();
+  // a second top as the backbone (the first id that is not the root) is the backbone's own node below the root (:770)
+  for (uint64_t x : ids) {
+    if (x == t.root) continue;
+    if (x == t.parent[x] && x != lca) children.push_back(x);
+    break;
+  }
   for (uint64_t x : ids) {
     if (x == t.parent[x] || x == lca) continue;
     for (;;) {

@@ -8,6 +8,8 @@
 namespace cfr {
 
 uint64_t tax_lca(const Taxonomy &t, const std::vector<uint64_t> &ids);
+// the same value through the fold the kernels use (cfr_tax_fold.hpp); depth: promote_depths(t.parent); steps: its loop iterations
+uint64_t tax_lca_fold(const Taxonomy &t, const std::vector<uint32_t> &depth, const uint64_t *ids, size_t cnt, uint32_t *steps = nullptr);
 void tax_lca_children(const Taxonomy &t, const std::vector<uint64_t> &ids, uint64_t lca, std::vector<uint64_t> &children);
 void tax_reduce(const Taxonomy &t, const std::vector<uint64_t> &ids, int k, std::vector<uint64_t> &out,
                 std::vector<std::vector<uint64_t>> *children = nullptr);

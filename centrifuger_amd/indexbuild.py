@@ -414,9 +414,11 @@ def write_taxonomy(path, names, taxids, nodes, tax_names):
         p = tid
         if p not in tree:
             continue
+        # ReadTaxonomyTree walks with std::map operator[] (Taxonomy.hpp:190-197): a parent the file does not name becomes a phantom node
+        # (parent 0, rank code 0, no leaf), and so does tax id 0 after it, which is its own parent; both are kept
         while p not in selected:
             selected.add(p)
-            p = tree[p][0]
+            p = tree.setdefault(p, (0, 0))[0]
     order = sorted(selected)                              # compact ids follow ascending original id (std::map order)
     cid = {tid: i for i, tid in enumerate(order)}
     leaf = {tid: 1 for tid in order}
@@ -441,7 +443,7 @@ def write_taxonomy(path, names, taxids, nodes, tax_names):
         for tid in order:
             s = sci.get(tid, "").encode()
             f.write(struct.pack("<Q", len(s)) + s)
-        f.write(struct.pack("<%dQ" % len(names), *[cid[t] for t in taxids]))
+        f.write(struct.pack("<%dQ" % len(names), *[cid.get(t, 0) for t in taxids]))      # outside the tree: MapID::Map hands out 0
         for nm in names:
             s = nm.encode()
             f.write(struct.pack("<Q", len(s)) + s)

@@ -432,6 +432,11 @@ const char *cfr_taxonomy_tax_name(const cfr_taxonomy *t, uint64_t compact_taxid)
 const char *cfr_taxonomy_seq_name(const cfr_taxonomy *t, uint64_t seq_id);          /* NULL beyond n_seq_names */
 const char *cfr_tax_rank_string(uint8_t rank);                                      /* Taxonomy::GetTaxRankString (Taxonomy.hpp:497-532) */
 void cfr_taxonomy_close(cfr_taxonomy *t);
+/* Taxonomy::LCA of n_lists lists of compact tax ids (list i = ids[begin[i] .. begin[i + 1]), every id below node_cnt), for tests.
+ * form 0: the host tail's literal restatement (cfr_tail.cpp tax_lca); form 1: the fold the kernels use (csrc/cfr_tax_fold.hpp) with the
+ * depth table of the device image.  out: n_lists results; steps (may be NULL; form 1): the fold's loop iterations per list. */
+cfr_status cfr_taxonomy_lca_probe(const cfr_taxonomy *t, const uint64_t *ids, const uint64_t *begin, size_t n_lists, int32_t form,
+                                  uint64_t *out, uint32_t *steps);
 
 /* ---- centrifuger-promote: assignments rewritten to a chosen rank, or folded into their LCA (the reference's Perl script
  * centrifuger-promote:44-149; the semantics are stated in csrc/cfr_promote_core.hpp) ----

@@ -591,6 +591,7 @@ static uint64_t tax_lca(const ora_taxonomy *t, const uint64_t *taxIds, int taxCn
   return ret;
 }
 uint64_t ora_tax_lca(const ora_taxonomy *t, const uint64_t *taxIds, int taxCnt) { return tax_lca(t, taxIds, taxCnt, NULL); }
+const ora_taxonomy *ora_index_taxonomy(const ora_index *idx) { return &idx->tax; }
 
 /* Taxonomy::ReduceTaxIds (Taxonomy.hpp:839-973).  returns number of promoted ids written to out.
  * child != NULL (promotedChildTaxIds): child[0..*nchild) receives one list per pushed vector - the caller compares *nchild with

@@ -234,6 +234,7 @@ void ora_results_free(ora_result *r, size_t n);
 const char *ora_tax_rank_string(uint8_t rank);
 
 /* taxonomy helpers exposed for tests */
+const ora_taxonomy *ora_index_taxonomy(const ora_index *idx);
 uint64_t ora_tax_lca(const ora_taxonomy *t, const uint64_t *taxIds, int n);
 int ora_tax_reduce(const ora_taxonomy *t, const uint64_t *taxIds, int n, int k, uint64_t *out, int outCap);
 

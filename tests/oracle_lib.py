@@ -84,6 +84,10 @@ def lib():
         L.ora_tsv_header.restype = C.c_char_p
         L.ora_tsv_header_for.restype = C.c_char_p
         L.ora_tsv_header_for.argtypes = [C.c_void_p]
+        L.ora_index_taxonomy.restype = C.c_void_p
+        L.ora_index_taxonomy.argtypes = [C.c_void_p]
+        L.ora_tax_lca.restype = C.c_uint64
+        L.ora_tax_lca.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _lib = L
     return _lib
 
@@ -122,6 +126,15 @@ class OracleIndex:
         l = C.c_uint64(0)
         v = lib().ora_fm_backward_to_sampled_sa(self._fm, int(row), C.byref(l), None)
         return int(v), int(l.value)
+
+    def tax_lca(self, lists):
+        """Taxonomy::LCA (ora_tax_lca) of every list of compact tax ids"""
+        t = lib().ora_index_taxonomy(self._h)
+        out = []
+        for ids in lists:
+            a = np.ascontiguousarray(ids, dtype=np.uint64)
+            out.append(int(lib().ora_tax_lca(t, a.ctypes.data, len(a))))
+        return out
 
     def query_hits(self, r1: bytes, r2: bytes | None = None, cap=4096):
         buf = np.zeros(cap, dtype=ORA_HIT_DTYPE)

@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import tax_worlds as tw
 from centrifuger_amd import capi, synth
 from cfr_fields import parse_1cfr
 from conftest import GOLDEN, REF_DIR, ROOT, have_ref
@@ -195,6 +196,49 @@ def test_cli_takes_the_inputs_the_reference_builder_takes(tmp_path, ignore_uncat
         out.append(subprocess.run([os.path.join(REF_DIR, "centrifuger"), "-x", pre, "-u", str(tmp_path / "r.fq"), "-t", "2"], check=True,
                                   stdout=subprocess.PIPE, stderr=subprocess.DEVNULL).stdout)
     assert out[0] == out[1]
+
+
+def _same_as(prefix, ref1, ref2):
+    mine, ref = parse_1cfr(prefix + ".1.cfr"), parse_1cfr(ref1)
+    assert len(mine) == len(ref)
+    for (na, va), (nb, vb) in zip(mine, ref):
+        assert na == nb and va == vb, f"field {na} differs"
+    assert open(prefix + ".2.cfr", "rb").read() == open(ref2, "rb").read(), ".2.cfr differs"
+
+
+@pytest.mark.parametrize("name", tw.COMMITTED)
+def test_native_writers_equal_reference_builder_on_forest_taxonomies(name, tmp_path):
+    """A subtree whose top names an absent parent, two self-parented nodes, no tax id 1 (tests/tax_worlds.py): cfr_build_index and
+    bin/centrifuger-build against the files the reference builder wrote (tests/golden/taxworlds).  ReadTaxonomyTree keeps the absent
+    parent and tax id 0 as phantom nodes (Taxonomy.hpp:190-197); the native writer used to stop the walk at the missing id."""
+    w = tw.make(name)
+    g = w.genomes
+    ref1, ref2 = os.path.join(GOLDEN, "taxworlds", "text.1.cfr"), os.path.join(GOLDEN, "taxworlds", name + ".2.cfr")
+    prefix = str(tmp_path / "own")
+    capi.build_index(g.names, g.taxids, g.seqs, g.nodes, g.tax_names, prefix, **tw.build_kwargs(w))
+    _same_as(prefix, ref1, ref2)
+    synth.write_reference_inputs(g, str(tmp_path))
+    cli = str(tmp_path / "cli")
+    r = subprocess.run([os.path.join(ROOT, "centrifuger_amd", "bin", "centrifuger-build"), "-t", "4", "-r", str(tmp_path / "ref.fa"), "--taxonomy-tree",
+                        str(tmp_path / "nodes.dmp"), "--name-table", str(tmp_path / "names.dmp"), "--conversion-table", str(tmp_path / "seqid.map"),
+                        "-o", cli, "--ftabchars", str(w.info["ftab_chars"])], stderr=subprocess.PIPE)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    _same_as(cli, ref1, ref2)
+
+
+@pytest.mark.skipif(not have_ref(), reason="oracle/_ref (compiled reference) not present")
+@pytest.mark.parametrize("name", tw.NAMES)
+def test_native_writer_equals_live_reference_build_of_every_taxonomy_world(name, tmp_path):
+    w = tw.make(name)
+    g = w.genomes
+    synth.write_reference_inputs(g, str(tmp_path))
+    ref = str(tmp_path / "ref")
+    subprocess.run([os.path.join(REF_DIR, "centrifuger-build"), "-t", "2", "-r", str(tmp_path / "ref.fa"), "--taxonomy-tree", str(tmp_path / "nodes.dmp"),
+                    "--name-table", str(tmp_path / "names.dmp"), "--conversion-table", str(tmp_path / "seqid.map"), "-o", ref,
+                    "--ftabchars", str(w.info["ftab_chars"])], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    prefix = str(tmp_path / "own")
+    capi.build_index(g.names, g.taxids, g.seqs, g.nodes, g.tax_names, prefix, **tw.build_kwargs(w))
+    _same_as(prefix, ref + ".1.cfr", ref + ".2.cfr")
 
 
 def test_build_entry_rejects_bad_genome_lists(tmp_path):

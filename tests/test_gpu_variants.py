@@ -146,6 +146,20 @@ def test_many_strain_workload_under_switches(name, extra):
     assert " passed" in tail
 
 
+@pytest.mark.parametrize("name,extra", [("no_team_tail", {"CFR_TEAM_TAIL": "0"}), ("team_tail_k1", {"CFR_TEST_K": "1"}), ("team_tail_k5", {"CFR_TEST_K": "5"})])
+def test_taxonomy_worlds_under_switches(name, extra):
+    """The entries of tests/test_gpu_tax_worlds.py (forests, a root other than tax id 1, sequences on the roots, a 300-node chain) with
+    the team fold off (every read of nine ids and more folds in one lane, through d_tax_lca) and at one -k alone.  The file's own child
+    processes set their switches themselves and are left out."""
+    env = dict(os.environ, CFR_DEBUG_ENV="1")
+    env.update(extra)
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_tax_worlds.py"), "-m", "gpu", "-x", "-q", "-k", "entries_equal_oracle"],
+                       env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, cwd=ROOT, timeout=600)
+    tail = r.stdout.decode()[-1500:]
+    assert r.returncode == 0, f"{name}:\n{tail}"
+    assert " passed" in tail
+
+
 @pytest.mark.parametrize("name,extra", [("protein_two_arrays", {"CFR_PROT_TWO_ARRAYS": "1"}), ("protein_no_kmer_table", {"CFR_FTABX_WIDTH": "0"}),
                                         ("protein_kmer_table_3", {"CFR_FTABX_WIDTH": "3"}), ("protein_kmer_table_5_two_arrays", {"CFR_FTABX_WIDTH": "5", "CFR_PROT_TWO_ARRAYS": "1"})])
 def test_protein_suite_under_switches(name, extra):
