@@ -112,6 +112,8 @@ EXPORTS = [
     "cfr_tsv_options_default", "cfr_tsv_open", "cfr_tsv_format", "cfr_tsv_get_stats", "cfr_tsv_close", "cfr_device_index_set_tsv",
     "cfr_device_index_tsv_last", "cfr_device_index_tsv_last_resident", "cfr_tokenizer_device_records", "cfr_last_tsv_ms",
     "cfr_gz_options_default", "cfr_gz_open", "cfr_gz_compress", "cfr_gz_dump", "cfr_gz_eof", "cfr_gz_get_stats", "cfr_gz_close",
+    "cfr_inflate_open", "cfr_inflate_bgzf", "cfr_inflate_member_status", "cfr_inflate_device_text", "cfr_inflate_get_stats", "cfr_inflate_close",
+    "cfr_tokenize_resident", "cfr_tokenizer_fetch_ids",
 ]
 
 _lib = None
@@ -139,7 +141,7 @@ def lib():
                             "cfr_barcode_translate_destroy", "cfr_tsv_header_ex", "cfr_format_tsv_ex",
                             "cfr_taxonomy_tax_name", "cfr_taxonomy_seq_name", "cfr_tax_rank_string", "cfr_taxonomy_close",
                             "cfr_tokenizer_close", "cfr_kreport_options_default", "cfr_tsv_options_default", "cfr_tsv_close",
-                            "cfr_gz_options_default", "cfr_gz_eof", "cfr_gz_close"):
+                            "cfr_gz_options_default", "cfr_gz_eof", "cfr_gz_close", "cfr_inflate_close"):
                 getattr(L, name).restype = C.c_int
         for name in ("cfr_quant_destroy", "cfr_read_format_destroy", "cfr_barcode_destroy", "cfr_barcode_translate_destroy"):
             getattr(L, name).restype = None
@@ -162,6 +164,8 @@ def lib():
         L.cfr_gz_close.argtypes = [C.c_void_p]
         L.cfr_gz_options_default.restype = None
         L.cfr_gz_eof.restype = None
+        L.cfr_inflate_close.restype = None
+        L.cfr_inflate_close.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -1115,6 +1119,24 @@ class Tokenizer:
         _check(lib().cfr_tokenizer_device_records(self._h, C.byref(t), C.byref(r)))
         return t.value or 0, r.value or 0
 
+    def tokenize_resident(self, d_text: int, length: int, final=True, max_records=0) -> TokenInfo:
+        """cfr_tokenize_resident: the text is `length` bytes at the device address d_text (Inflate.device_text(), or a range inside it)"""
+        info = TokenInfo()
+        _check(lib().cfr_tokenize_resident(self._h, C.c_void_p(d_text), C.c_uint64(length), C.c_int(int(bool(final))), C.c_uint64(max_records), C.byref(info)))
+        self._last = info
+        return info
+
+    def fetch_ids(self, cap=None):
+        """cfr_tokenizer_fetch_ids -> (ids uint8[total], id_off uint64[n + 1]) of the last call; cap: the bytes offered (default: asked for first)"""
+        n = self._last.n_records
+        off = np.zeros(n + 1, dtype=np.uint64)
+        if cap is None:
+            _check(lib().cfr_tokenizer_fetch_ids(self._h, None, C.c_uint64(0), _p(off)))
+            cap = int(off[n])
+        ids = np.zeros(max(cap, 1), dtype=np.uint8)
+        _check(lib().cfr_tokenizer_fetch_ids(self._h, _p(ids), C.c_uint64(cap), _p(off)))
+        return ids[:int(off[n])], off
+
     @staticmethod
     def ids(text, records):
         t = bytes(text)
@@ -1287,6 +1309,69 @@ class Gz:
     def close(self):
         if self._h:
             lib().cfr_gz_close(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+INF_STATUS = {"ok": 0, "bad_header": 1, "bad_block_type": 2, "bad_stored_len": 3, "bad_code_set": 4, "bad_symbol": 5, "input": 6, "output_long": 7,
+              "output_short": 8, "bad_crc": 9}
+
+
+class InflateInfo(C.Structure):
+    _fields_ = [("members", C.c_uint64), ("bad_members", C.c_uint64), ("first_bad", C.c_uint64), ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64),
+                ("first_bad_status", C.c_int32)]
+
+
+class InflateStats(C.Structure):
+    _fields_ = [("upload_ms", C.c_float), ("inflate_ms", C.c_float), ("download_ms", C.c_float)]
+
+
+class Inflate:
+    """cfr_inflate: BGZF members back into text, every member with a status.  device=None: the host twin."""
+
+    def __init__(self, device=None):
+        self._h = C.c_void_p()
+        self._members = 0
+        _check(lib().cfr_inflate_open(C.c_int(-1 if device is None else device), C.byref(self._h)))
+
+    def inflate(self, members, fetch_text=True, copy=True):
+        """members: bytes or a uint8 array of whole BGZF members -> (text bytes or None, InflateInfo); copy=False: (text size, info)"""
+        a = np.frombuffer(bytes(members) or b"\0", dtype=np.uint8) if not isinstance(members, np.ndarray) else np.ascontiguousarray(members, dtype=np.uint8)
+        text, text_n, info = C.POINTER(C.c_uint8)(), C.c_uint64(), InflateInfo()
+        _check(lib().cfr_inflate_bgzf(self._h, _p(a), C.c_uint64(len(members)), C.c_int(int(bool(fetch_text))), C.byref(text), C.byref(text_n), C.byref(info)))
+        self._members = info.members
+        if not copy:
+            return text_n.value, info
+        if not fetch_text or not text:
+            return (b"" if fetch_text else None), info
+        return (C.string_at(text, text_n.value) if text_n.value else b""), info
+
+    def member_status(self):
+        """-> (status uint8[members], text_off uint64[members + 1]) of the last inflate()"""
+        status = np.zeros(max(self._members, 1), dtype=np.uint8)
+        off = np.zeros(self._members + 1, dtype=np.uint64)
+        _check(lib().cfr_inflate_member_status(self._h, _p(status), _p(off), C.c_uint64(self._members)))
+        return status[:self._members], off
+
+    def device_text(self):
+        """-> (device address, bytes) of the last call's text; valid until the next inflate() / close()"""
+        d, n = C.c_void_p(), C.c_uint64()
+        _check(lib().cfr_inflate_device_text(self._h, C.byref(d), C.byref(n)))
+        return d.value or 0, n.value
+
+    def stats(self) -> InflateStats:
+        st = InflateStats()
+        _check(lib().cfr_inflate_get_stats(self._h, C.byref(st)))
+        return st
+
+    def close(self):
+        if self._h:
+            lib().cfr_inflate_close(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

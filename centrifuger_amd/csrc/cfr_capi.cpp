@@ -24,6 +24,7 @@
 #include "cfr_tokenize_core.hpp"
 #include "cfr_tsv.hpp"
 #include "cfr_gz.hpp"
+#include "cfr_inflate.hpp"
 
 struct cfr_index { cfr::HostIndex *h; };
 struct cfr_read_format { cfr::ReadFormat f; };
@@ -40,6 +41,7 @@ struct cfr_kreport { cfr::Kreport *k; };
 struct cfr_tokenizer { cfr::Tokenizer *t; };
 struct cfr_tsv { cfr::Tsv *t; };
 struct cfr_gz { cfr::Gz *g; };
+struct cfr_inflate { cfr::Inflate *i; };
 struct cfr_quant { cfr::Quant *q; std::vector<double> weight; int32_t rounds = 0; bool ran = false; };
 // One call at a time per device image: `busy` is held for the length of every entry that touches the image (try_lock:
 // CFR_ERR_BUSY for the second caller) and by the worker thread while it runs a submitted batch.
@@ -118,6 +120,14 @@ std::set<const cfr_gz *> g_gz_live;
 bool gz_live(const cfr_gz *h) {
   std::lock_guard<std::mutex> lk(g_gz_mu);
   return h && g_gz_live.count(h) != 0;
+}
+
+// ... and the cfr_inflate handles
+std::mutex g_inflate_mu;
+std::set<const cfr_inflate *> g_inflate_live;
+bool inflate_live(const cfr_inflate *h) {
+  std::lock_guard<std::mutex> lk(g_inflate_mu);
+  return h && g_inflate_live.count(h) != 0;
 }
 
 // entry guard: the image's buffers, streams and statistics belong to one call at a time
@@ -1153,6 +1163,75 @@ void cfr_gz_close(cfr_gz *h) {
   }
   delete h->g;
   delete h;
+}
+
+// ---- BGZF members back into text (cfr_inflate_core.hpp) ----
+cfr_status cfr_inflate_open(int device, cfr_inflate **out) {
+  if (!out) return bad_arg("cfr_inflate_open: null argument");
+  *out = nullptr;
+  if (device < -1) return bad_arg("cfr_inflate_open: device is a HIP ordinal, or -1 for the host twin");
+  return guarded([&]() -> cfr_status {
+    std::unique_ptr<cfr_inflate> h(new cfr_inflate{nullptr});
+    h->i = device < 0 ? cfr::make_inflate_host() : cfr::make_inflate_device(device);
+    { std::lock_guard<std::mutex> lk(g_inflate_mu); g_inflate_live.insert(h.get()); }
+    *out = h.release();
+    return CFR_OK;
+  });
+}
+
+cfr_status cfr_inflate_bgzf(cfr_inflate *h, const uint8_t *members, uint64_t n, int fetch_text, const uint8_t **text, uint64_t *text_n, cfr_inflate_info *info) {
+  if (!inflate_live(h)) return bad_arg("cfr_inflate_bgzf: not an open cfr_inflate handle");
+  return guarded([&]() -> cfr_status { h->i->inflate(members, n, fetch_text, text, text_n, info); return CFR_OK; });
+}
+
+cfr_status cfr_inflate_member_status(cfr_inflate *h, uint8_t *status, uint64_t *text_off, uint64_t cap) {
+  if (!inflate_live(h)) return bad_arg("cfr_inflate_member_status: not an open cfr_inflate handle");
+  if (h->i->member_status(status, text_off, cap)) return CFR_OK;
+  g_err = "cfr_inflate_member_status: the last call had more than " + std::to_string(cap) + " members";
+  return CFR_ERR_CAPACITY;
+}
+
+cfr_status cfr_inflate_device_text(cfr_inflate *h, const void **d_text, uint64_t *n) {
+  if (!inflate_live(h)) return bad_arg("cfr_inflate_device_text: not an open cfr_inflate handle");
+  if (!h->i->device_text(d_text, n)) return bad_arg("cfr_inflate_device_text: the handle is the host twin (opened with device -1)");
+  return CFR_OK;
+}
+
+cfr_status cfr_inflate_get_stats(cfr_inflate *h, cfr_inflate_stats *st) {
+  if (!inflate_live(h)) return bad_arg("cfr_inflate_get_stats: not an open cfr_inflate handle");
+  if (!st) return bad_arg("cfr_inflate_get_stats: null argument");
+  h->i->stats(st);
+  return CFR_OK;
+}
+
+void cfr_inflate_close(cfr_inflate *h) {
+  {
+    std::lock_guard<std::mutex> lk(g_inflate_mu);
+    if (!h || !g_inflate_live.erase(h)) return;
+  }
+  delete h->i;
+  delete h;
+}
+
+cfr_status cfr_tokenize_resident(cfr_tokenizer *t, const void *d_text, uint64_t len, int final, uint64_t max_records, cfr_token_info *info) {
+  if (!tokenizer_live(t)) return bad_arg("cfr_tokenize_resident: not an open cfr_tokenizer handle");
+  if (!info || (len && !d_text)) return bad_arg("cfr_tokenize_resident: null argument");
+  if (len >> 32) return bad_arg("cfr_tokenize_resident: len must be below 2^32 (offsets inside a call are 32 bits wide on the device): hand the text over in pieces");
+  return guarded([&]() -> cfr_status {
+    if (t->t->tokenize_resident(d_text, len, final, max_records, info)) return CFR_OK;
+    g_err = "cfr_tokenize_resident: the handle is the host twin (opened with device -1)";
+    return CFR_ERR_ARG;
+  });
+}
+
+cfr_status cfr_tokenizer_fetch_ids(cfr_tokenizer *t, char *ids, uint64_t ids_cap, uint64_t *id_off) {
+  if (!tokenizer_live(t)) return bad_arg("cfr_tokenizer_fetch_ids: not an open cfr_tokenizer handle");
+  return guarded([&]() -> cfr_status {
+    uint64_t need = 0;
+    if (t->t->fetch_ids(ids, ids_cap, id_off, &need)) return CFR_OK;
+    g_err = "cfr_tokenizer_fetch_ids: the ids take " + std::to_string(need) + " bytes, the buffer holds " + std::to_string(ids_cap);
+    return CFR_ERR_CAPACITY;
+  });
 }
 
 cfr_status cfr_device_index_set_tsv(cfr_dev_index *d, int on) {

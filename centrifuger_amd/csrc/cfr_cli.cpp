@@ -67,13 +67,14 @@ const char *kUsage =
     "\t--gpu-throughput: ... and the 68 GB K-mer table (longest load, fastest kernels) [default: neither, shortest load]\n"
     "\t--parse-threads INT: threads that parse plain single-end read files in pieces [min(-t,8); 1 = sequential reader]\n"
     "\t--gpu-parse: tokenise plain FASTA/FASTQ files (-u, -1/-2) on the GPU that classifies them; the run falls back to the host parsers, with one log line, for what that does not cover [host parsers]\n"
+    "\t--gpu-inflate: inflate -u files that are BGZF throughout on the GPU that classifies them and tokenise the text there (implies --gpu-parse); every other file is inflated on the host, with one log line [host inflaters]\n"
     "\t--gpu-format: make the TSV rows on the GPU that classified the reads (with --gpu-parse the read ids never leave it); the rows are formatted on the host, with one log line, for what that does not cover [host formatter]\n"
     "\t--gpu-dump: make and compress the --un / --cl read dumps on the GPU that classified the reads; the files are BGZF (gzip in members of at most 64 KiB, read by every gunzip); --merge-readpair keeps the host writer, with one log line [host writer, zlib level 1]\n"
     "\t--gpu-dump-codes fixed|dynamic: the Huffman codes of --gpu-dump's members: the fixed code of deflate, or each member's own codes where they make it smaller (smaller files, more work on the GPU) [fixed]\n"
     "\t-h: print this usage message\n"
     "\t-v: print the version information and quit\n";
 
-enum { OPT_UN = 1000, OPT_CL, OPT_NO_DUST, OPT_MIN_HITLEN, OPT_HITK, OPT_SECONDARY, OPT_GPU, OPT_GPU_BATCH, OPT_GPU_THROUGHPUT, OPT_GPU_FASTLOAD, OPT_GPU_BALANCED, OPT_PARSE_THREADS, OPT_GPU_PARSE, OPT_GPU_FORMAT, OPT_GPU_DUMP, OPT_GPU_DUMP_CODES, OPT_EXPAND_TAXID, OPT_MERGE_READPAIR, OPT_QUANT, OPT_QUANT_FORMAT, OPT_PROMOTE, OPT_KREPORT, OPT_BARCODE, OPT_UMI, OPT_READ_FORMAT, OPT_BARCODE_WHITELIST, OPT_BARCODE_TRANSLATE, OPT_UNSUPPORTED };
+enum { OPT_UN = 1000, OPT_CL, OPT_NO_DUST, OPT_MIN_HITLEN, OPT_HITK, OPT_SECONDARY, OPT_GPU, OPT_GPU_BATCH, OPT_GPU_THROUGHPUT, OPT_GPU_FASTLOAD, OPT_GPU_BALANCED, OPT_PARSE_THREADS, OPT_GPU_PARSE, OPT_GPU_INFLATE, OPT_GPU_FORMAT, OPT_GPU_DUMP, OPT_GPU_DUMP_CODES, OPT_EXPAND_TAXID, OPT_MERGE_READPAIR, OPT_QUANT, OPT_QUANT_FORMAT, OPT_PROMOTE, OPT_KREPORT, OPT_BARCODE, OPT_UMI, OPT_READ_FORMAT, OPT_BARCODE_WHITELIST, OPT_BARCODE_TRANSLATE, OPT_UNSUPPORTED };
 
 // Persistent workers for the dust and the format stage: a 256 k-read batch is 6 ms of work on 64 threads, less than
 // what starting 64 threads costs, so the threads are started once.
@@ -146,6 +147,7 @@ struct Options {
   int parse_threads = 0;               // 0 = automatic
   bool balanced_profile = false;
   bool gpu_parse = false;              // --gpu-parse: cfr_tokenize on the device instead of SeqReader, where it applies
+  bool gpu_inflate = false;            // --gpu-inflate: BGZF -u files go to the device compressed (cfr_inflate_bgzf, cfr_tokenize_resident), where it applies
   bool gpu_format = false;             // --gpu-format: the rows of a batch made on the device (cfr_device_index_tsv_last), where it applies
   bool gpu_dump_dynamic = false;       // --gpu-dump-codes dynamic: cfr_gz_options.codes = 1 for those dumps
   bool gpu_dump = false;               // --gpu-dump: the --un / --cl dumps made and compressed on the device (cfr_gz_dump), where it applies
@@ -295,7 +297,7 @@ int parse_options(int argc, char *argv[], Options &opt) {
       {"consider-secondary", required_argument, 0, OPT_SECONDARY}, {"gpu", required_argument, 0, OPT_GPU},
       {"gpu-batch", required_argument, 0, OPT_GPU_BATCH}, {"gpu-throughput", no_argument, 0, OPT_GPU_THROUGHPUT},
       {"gpu-fast-load", no_argument, 0, OPT_GPU_FASTLOAD}, {"gpu-balanced", no_argument, 0, OPT_GPU_BALANCED},
-      {"parse-threads", required_argument, 0, OPT_PARSE_THREADS}, {"gpu-parse", no_argument, 0, OPT_GPU_PARSE}, {"gpu-format", no_argument, 0, OPT_GPU_FORMAT}, {"gpu-dump", no_argument, 0, OPT_GPU_DUMP}, {"gpu-dump-codes", required_argument, 0, OPT_GPU_DUMP_CODES},
+      {"parse-threads", required_argument, 0, OPT_PARSE_THREADS}, {"gpu-parse", no_argument, 0, OPT_GPU_PARSE}, {"gpu-inflate", no_argument, 0, OPT_GPU_INFLATE}, {"gpu-format", no_argument, 0, OPT_GPU_FORMAT}, {"gpu-dump", no_argument, 0, OPT_GPU_DUMP}, {"gpu-dump-codes", required_argument, 0, OPT_GPU_DUMP_CODES},
       {"sample-sheet", required_argument, 0, OPT_UNSUPPORTED}, {"merge-readpair", no_argument, 0, OPT_MERGE_READPAIR},
       {"quant", required_argument, 0, OPT_QUANT}, {"quant-format", required_argument, 0, OPT_QUANT_FORMAT},
       {"promote", required_argument, 0, OPT_PROMOTE}, {"kreport", required_argument, 0, OPT_KREPORT},
@@ -354,6 +356,7 @@ int parse_options(int argc, char *argv[], Options &opt) {
       case OPT_GPU_BALANCED: opt.balanced_profile = true; break;
       case OPT_PARSE_THREADS: opt.parse_threads = atoi(optarg); break;
       case OPT_GPU_PARSE: opt.gpu_parse = true; break;
+      case OPT_GPU_INFLATE: opt.gpu_inflate = true; break;
       case OPT_GPU_FORMAT: opt.gpu_format = true; break;
       case OPT_GPU_DUMP: opt.gpu_dump = true; break;
       case OPT_GPU_DUMP_CODES:
@@ -556,6 +559,8 @@ struct Run {
   bool gpu_dump = false;
   std::atomic<long long> dump_ns{0}, dump_kernel_ns{0};   // ... the workers' time in cfr_gz_dump, and the device time of its kernels
   bool gpu_parse = false;              // --gpu-parse, where it applies
+  bool gpu_inflate = false;            // --gpu-inflate, where it applies (then gpu_parse is on as well)
+  std::vector<std::unique_ptr<BgzfFile>> bgzf_files;   // (mapped until the end of the run: batches point into them)
   bool gpu_format = false;             // --gpu-format, where it applies
   std::atomic<long long> tsv_kernel_ns{0};   // ... and the device time of its kernels (cfr_last_tsv_ms), all batches
   bool protein = false, dumps = false, host_dust = false, host_merge = false, expand = false;
@@ -816,12 +821,38 @@ struct Reader {
   // --gpu-parse: every file must be a plain file that the record cutter accepts (pieces of --gpu-batch records that start and end at
   // verified record starts); otherwise nothing of the run takes this path.  The pieces go to the device workers unparsed.
   bool publish_raw() {
-    struct RawPlan { const MappedFile *f1, *f2; std::vector<size_t> c1, c2; size_t total; };
+    struct RawPlan { const MappedFile *f1, *f2; std::vector<size_t> c1, c2; size_t total; const BgzfFile *z; };
     std::vector<RawPlan> plans;
     const char *why = nullptr;
     const std::vector<std::string> &first = opt.paired ? opt.m1 : opt.u;
+    // --gpu-inflate: every -u file is planned by its own kind, plain or BGZF throughout; one file of neither kind and the run is what
+    // it is without the switch
+    std::vector<const BgzfFile *> zfile(first.size(), nullptr);
+    if (run.gpu_inflate) {
+      const char *why_z = nullptr;
+      for (size_t i = 0; i < first.size() && !why_z; ++i) {
+        MappedFile probe;
+        if (first[i] != "-" && probe.open_plain(first[i])) continue;
+        run.bgzf_files.emplace_back(new BgzfFile());
+        BgzfFile &z = *run.bgzf_files.back();
+        if (first[i] == "-" || !z.open(first[i])) why_z = "an input is neither a plain file nor BGZF throughout (plain gzip, stdin, or BGZF followed by plain members)";
+        else if (!z.plan(opt.gpu_batch)) why_z = "the text of a BGZF file does not begin with a regular record (4-line FASTQ, or FASTA)";
+        else {
+          for (size_t k = 0; k + 1 < z.cut.size() && !why_z; ++k)
+            if ((z.cut[k + 1] - z.cut[k] + 2 * 65536) >> 32) why_z = "a piece of the text has 4 GB or more";
+          zfile[i] = &z;
+        }
+      }
+      if (why_z) {
+        print_log("--gpu-inflate is not used, the file is inflated on the host: %s.", why_z);
+        run.gpu_inflate = false;
+        if (!opt.gpu_parse) { run.gpu_parse = false; return false; }
+        zfile.assign(first.size(), nullptr);
+      }
+    }
     for (size_t i = 0; i < first.size() && !why; ++i) {
-      RawPlan p{nullptr, nullptr, {}, {}, 0};
+      RawPlan p{nullptr, nullptr, {}, {}, 0, zfile[i]};
+      if (p.z) { plans.push_back(std::move(p)); continue; }
       size_t t2 = 0;
       auto plan = [&](const std::string &f, const MappedFile *&mf, std::vector<size_t> &cuts, size_t &total) {
         run.raw_files.emplace_back(new MappedFile());
@@ -837,8 +868,28 @@ struct Reader {
       }
       plans.push_back(std::move(p));
     }
-    if (why) { print_log("--gpu-parse is not used, the reads are parsed on the host: %s.", why); return false; }
-    for (const RawPlan &p : plans)
+    if (why) {
+      if (opt.gpu_parse) print_log("--gpu-parse is not used, the reads are parsed on the host: %s.", why);
+      else print_log("--gpu-inflate is not used, the file is inflated on the host: %s.", why);
+      run.gpu_inflate = false;
+      return false;
+    }
+    for (const RawPlan &p : plans) {
+      if (p.z) {                                         // the members that hold the piece's text, and where the piece lies in it
+        const BgzfFile &z = *p.z;
+        for (size_t k = 0; k + 1 < z.cut.size(); ++k) {
+          if (z.cut[k + 1] == z.cut[k]) continue;
+          std::shared_ptr<Batch> b = fresh_batch();
+          b->raw = true;
+          b->bgzf = &z;
+          b->z_m0 = z.member_of(z.cut[k]); b->z_m1 = z.member_of(z.cut[k + 1] - 1) + 1;
+          b->z_off = z.off[b->z_m0];
+          b->raw1 = (const char *)z.base + b->z_off; b->raw1_len = z.off[b->z_m1] - b->z_off;
+          b->z_skip = z.cut[k] - z.text[b->z_m0]; b->z_len = z.cut[k + 1] - z.cut[k];
+          publish(b);
+        }
+        continue;
+      }
       for (size_t k = 0; k + 1 < p.c1.size(); ++k) {
         std::shared_ptr<Batch> b = fresh_batch();
         b->raw = true;
@@ -848,6 +899,7 @@ struct Reader {
         if (p.f2) { b->raw2 = p.f2->base + p.c2[k]; b->raw2_len = p.c2[k + 1] - p.c2[k]; }
         publish(b);
       }
+    }
     return true;
   }
 
@@ -957,6 +1009,9 @@ struct DeviceWorker {
   size_t dev_no;
   cfr_tokenizer *tok1 = nullptr, *tok2 = nullptr;       // --gpu-parse: opened with the first raw batch, on this worker's GPU
   cfr_token_info tk1, tk2;
+  cfr_inflate *inf = nullptr;                           // --gpu-inflate: opened with the first BGZF batch, beside the tokeniser
+  std::vector<char> z_ids;
+  std::vector<uint64_t> z_id_off;
   std::vector<cfr_read_record> recs;
   std::vector<char> id_bytes;                           // --gpu-format: the batch's ids without their terminators, and their n + 1 offsets
   std::vector<uint64_t> id_offs;
@@ -991,6 +1046,40 @@ struct DeviceWorker {
     }
     return true;
   }
+  // --gpu-inflate: the batch's members are inflated in HBM and the piece of their text is tokenised where it lies.  true: the reads
+  // are in HBM; false: the piece is not regular.  A member that does not inflate ends the run, as it does on the host path.
+  bool tokenize_bgzf(Batch &b) {
+    cfr_status s;
+    if (!tok1 && (s = cfr_tokenizer_open(run.opt.gpus[dev_no], &tok1)) != CFR_OK) die_status("cfr_tokenizer_open", s);
+    if (!inf && (s = cfr_inflate_open(run.opt.gpus[dev_no], &inf)) != CFR_OK) die_status("cfr_inflate_open", s);
+    const uint8_t *text = nullptr;
+    uint64_t text_n = 0;
+    cfr_inflate_info info;
+    if ((s = cfr_inflate_bgzf(inf, (const uint8_t *)b.raw1, b.raw1_len, 0, &text, &text_n, &info)) != CFR_OK) die_status("cfr_inflate_bgzf", s);
+    if (info.bad_members) b.bgzf->bad_member(b.bgzf->off[b.z_m0 + info.first_bad]);
+    const void *d_text = nullptr;
+    if ((s = cfr_inflate_device_text(inf, &d_text, &text_n)) != CFR_OK) die_status("cfr_inflate_device_text", s);
+    if ((s = cfr_tokenize_resident(tok1, (const uint8_t *)d_text + b.z_skip, b.z_len, 1, 0, &tk1)) != CFR_OK) die_status("cfr_tokenize_resident", s);
+    if (tk1.irregular || tk1.consumed != b.z_len) return false;
+    b.n = tk1.n_records;
+    if (run.gpu_format) return true;               // the ids stay in HBM
+    z_ids.resize(b.z_len + 1);                     // (no id is longer than its header line)
+    z_id_off.resize(b.n + 1);
+    if ((s = cfr_tokenizer_fetch_ids(tok1, z_ids.data(), z_ids.size(), z_id_off.data())) != CFR_OK) die_status("cfr_tokenizer_fetch_ids", s);
+    for (size_t i = 0; i < b.n; ++i) {
+      b.id_off.push_back(b.ids.size());
+      b.ids.insert(b.ids.end(), z_ids.data() + z_id_off[i], z_ids.data() + z_id_off[i + 1]);
+      b.ids.push_back('\0');
+    }
+    return true;
+  }
+  // ... and such a piece inflated with zlib and parsed with SeqReader
+  void parse_bgzf_on_host(Batch &b) {
+    b.z_text.clear();
+    b.bgzf->inflate_members(b.z_m0, b.z_m1, b.z_text);
+    TakeSpec ts;
+    parse_piece(b, ts, b.z_text.data() + b.z_skip, b.z_len, nullptr, 0, 0);
+  }
   // ... and the same pieces through SeqReader, as the parallel readers of the host path take them
   void parse_raw_on_host(Batch &b) {
     TakeSpec ts;
@@ -1006,11 +1095,13 @@ struct DeviceWorker {
   bool take_raw(Batch &b) {
     bool resident = false;
     if (!run.raw_broken.load()) {
-      resident = tokenize_raw(b);
-      if (!resident && !run.raw_broken.exchange(true))
-        print_log("--gpu-parse stops here, the rest is parsed on the host: a piece of the input is not made of regular records.");
+      resident = b.bgzf ? tokenize_bgzf(b) : tokenize_raw(b);
+      if (!resident && !run.raw_broken.exchange(true)) {
+        if (run.gpu_inflate) print_log("--gpu-inflate stops here, the rest is inflated and parsed on the host: a piece of the input is not made of regular records.");
+        else print_log("--gpu-parse stops here, the rest is parsed on the host: a piece of the input is not made of regular records.");
+      }
     }
-    if (!resident) parse_raw_on_host(b);
+    if (!resident) { if (b.bgzf) parse_bgzf_on_host(b); else parse_raw_on_host(b); }
     return resident;
   }
 
@@ -1186,6 +1277,7 @@ struct DeviceWorker {
     cfr_gz_close(gz);
     cfr_tokenizer_close(tok1);
     cfr_tokenizer_close(tok2);
+    cfr_inflate_close(inf);
     run.classified.close();
   }
 };
@@ -1304,7 +1396,7 @@ int plan_run(Run &run) {
   // ---- --gpu-parse: where it applies the reader hands out unparsed pieces of the mapped files and the device workers tokenise them;
   // everywhere else the run is what it is without the switch, and one log line says why
   run.gpu_parse = opt.gpu_parse;
-  if (run.gpu_parse) {
+  {
     const char *why = nullptr;
     if (!opt.un_prefix.empty() || !opt.cl_prefix.empty()) why = "--un / --cl need the reads and their qualities on the host";
     else if (opt.merge) why = "--merge-readpair needs the qualities";
@@ -1312,7 +1404,13 @@ int plan_run(Run &run) {
     else if (!opt.inter.empty()) why = "interleaved files (-i) are not covered";
     else if (opt.single_cell) why = "the single-cell options read several files in step";
     else if (run.protein) why = "a protein index is not covered";
-    if (why) { print_log("--gpu-parse is not used, the reads are parsed on the host: %s.", why); run.gpu_parse = false; }
+    if (run.gpu_parse && why) { print_log("--gpu-parse is not used, the reads are parsed on the host: %s.", why); run.gpu_parse = false; }
+    // ---- --gpu-inflate: the same rule, under the conditions of --gpu-parse, which it implies; -u files only (the reader decides per file)
+    if (opt.gpu_inflate) {
+      if (!why && opt.paired) why = "two BGZF mate files (-1/-2) cannot be cut at the same pair without inflating them";
+      if (why) print_log("--gpu-inflate is not used, the file is inflated on the host: %s.", why);
+      else run.gpu_inflate = run.gpu_parse = true;
+    }
   }
   // ---- --gpu-format: the same rule
   run.gpu_format = opt.gpu_format;

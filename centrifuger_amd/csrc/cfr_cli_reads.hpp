@@ -398,6 +398,39 @@ class SeqReader {
 
 int SeqReader::inflate_threads = 1;
 
+// The record cutter's search over any buffer of text: the first verified record start at or after `from`, or size.  fmt: '>' or '@',
+// the file's first byte.  from = 0 is taken for a line start; elsewhere the search begins behind the next '\n' unless a '\n' stands in
+// front.  whole: the buffer ends where the text ends - otherwise a FASTQ record verifies only when its fourth line ends inside the buffer.
+inline size_t resync_text(const char *base, size_t size, char fmt, size_t from, bool whole) {
+  size_t at = from;
+  if (at > 0 && base[at - 1] != '\n') {
+    const char *nl = at < size ? (const char *)memchr(base + at, '\n', size - at) : nullptr;
+    if (!nl) return size;
+    at = (size_t)(nl - base) + 1;
+  }
+  auto line_end = [&](size_t a) -> size_t { const char *nl = (const char *)memchr(base + a, '\n', size - a); return nl ? (size_t)(nl - base) : size; };
+  auto trimmed = [&](size_t a, size_t e) -> size_t { while (e > a && base[e - 1] == '\r') --e; return e - a; };
+  while (at < size) {
+    const size_t e0 = line_end(at);
+    if (base[at] == fmt) {
+      if (fmt == '>') return at;
+      const size_t l1 = e0 + 1;
+      if (l1 < size) {
+        const size_t e1 = line_end(l1), l2 = e1 + 1;
+        if (l2 < size && base[l2] == '+') {
+          const size_t e2 = line_end(l2), l3 = e2 + 1;
+          if (l3 <= size) {
+            const size_t e3 = l3 < size ? line_end(l3) : size;
+            if ((whole || e3 < size) && trimmed(l1, e1) == trimmed(l3, e3) && (e3 + 1 >= size || base[e3 + 1] == '@')) return at;
+          }
+        }
+      }
+    }
+    at = e0 + 1;
+  }
+  return size;
+}
+
 // A plain (not gz) regular read file mapped into memory, and the offsets at which it can be cut into independently parsable
 // pieces.  A cut is a verified record start: FASTA - a line that starts with '>'; FASTQ - a line that starts with '@' whose
 // third line starts with '+' and whose second and fourth lines have the same length (a quality line that starts with '@' fails
@@ -420,36 +453,7 @@ struct MappedFile {
     return base[0] == '@' || base[0] == '>';
   }
   // first verified record start at or after `from` (a line start), or size
-  size_t resync(size_t from) const {
-    const char fmt = base[0];
-    size_t at = from;
-    if (at > 0 && base[at - 1] != '\n') {
-      const char *nl = (const char *)memchr(base + at, '\n', size - at);
-      if (!nl) return size;
-      at = (size_t)(nl - base) + 1;
-    }
-    auto line_end = [&](size_t a) -> size_t { const char *nl = (const char *)memchr(base + a, '\n', size - a); return nl ? (size_t)(nl - base) : size; };
-    auto trimmed = [&](size_t a, size_t e) -> size_t { while (e > a && base[e - 1] == '\r') --e; return e - a; };
-    while (at < size) {
-      const size_t e0 = line_end(at);
-      if (base[at] == fmt) {
-        if (fmt == '>') return at;
-        const size_t l1 = e0 + 1;
-        if (l1 < size) {
-          const size_t e1 = line_end(l1), l2 = e1 + 1;
-          if (l2 < size && base[l2] == '+') {
-            const size_t e2 = line_end(l2), l3 = e2 + 1;
-            if (l3 <= size) {
-              const size_t e3 = l3 < size ? line_end(l3) : size;
-              if (trimmed(l1, e1) == trimmed(l3, e3) && (e3 + 1 >= size || base[e3 + 1] == '@')) return at;
-            }
-          }
-        }
-      }
-      at = e0 + 1;
-    }
-    return size;
-  }
+  size_t resync(size_t from) const { return resync_text(base, size, base[0], from, true); }
 };
 
 // Cuts about every `piece` bytes, each moved on to the next verified record start: cuts = 0, ..., the file size
@@ -462,6 +466,147 @@ inline void plan_byte_cuts(const MappedFile &mf, size_t piece, std::vector<size_
   }
   cuts.push_back(mf.size);
 }
+
+// --gpu-inflate: a read file that is BGZF throughout, mapped, and the cuts of its TEXT into record-aligned pieces found without the
+// text: the members are grouped by their ISIZE into pieces of about `piece` text bytes, and at every boundary a scout inflates members
+// on the host (zlib), the boundary's member alone first, one more at a time up to kScoutBytes of text, until the record cutter
+// (resync_text) finds a verified record start in that window; a boundary where none is found is dropped.  cut[k]: the text offset of
+// piece k's first record; piece k is the text [cut[k], cut[k + 1]).
+struct BgzfFile {
+  static constexpr size_t kScoutBytes = 4u << 20;
+  std::string path;
+  const uint8_t *base = nullptr;
+  size_t size = 0;
+  std::vector<size_t> off, text;       // members + 1 entries: where member m stands in the file, and its text in the file's text
+  std::vector<size_t> cut;
+  char fmt = 0;
+  ~BgzfFile() { if (base) munmap((void *)base, size); }
+
+  static bool header(const uint8_t *b, size_t left, size_t &bsize, size_t &head) {      // the rule of SeqReader::bgzf_header
+    if (left < 18 || b[0] != 0x1f || b[1] != 0x8b || b[2] != 8 || !(b[3] & 4)) return false;
+    const size_t xlen = (size_t)b[10] | ((size_t)b[11] << 8);
+    if (12 + xlen > left) return false;
+    for (size_t o = 12; o + 4 <= 12 + xlen;) {
+      const size_t slen = (size_t)b[o + 2] | ((size_t)b[o + 3] << 8);
+      if (b[o] == 'B' && b[o + 1] == 'C' && slen == 2 && o + 6 <= 12 + xlen) {
+        bsize = ((size_t)b[o + 4] | ((size_t)b[o + 5] << 8)) + 1;
+        head = 12 + xlen;
+        return bsize >= 12 + xlen + 8 && bsize <= left;
+      }
+      o += 4 + slen;
+    }
+    return false;
+  }
+  // true: a regular file made of BGZF members from its first byte to its last
+  bool open(const std::string &p) {
+    path = p;
+    const int fd = ::open(p.c_str(), O_RDONLY);
+    if (fd < 0) return false;
+    struct stat st;
+    if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size < 28) { ::close(fd); return false; }
+    void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+    ::close(fd);
+    if (m == MAP_FAILED) return false;
+    base = (const uint8_t *)m;
+    size = (size_t)st.st_size;
+    size_t t = 0;
+    for (size_t o = 0; o < size;) {
+      size_t bs = 0, head = 0;
+      if (!header(base + o, size - o, bs, head)) return false;
+      off.push_back(o);
+      text.push_back(t);
+      const uint8_t *tail = base + o + bs - 4;
+      t += (size_t)tail[0] | ((size_t)tail[1] << 8) | ((size_t)tail[2] << 16) | ((size_t)tail[3] << 24);
+      o += bs;
+    }
+    off.push_back(size);
+    text.push_back(t);
+    return true;
+  }
+  size_t members() const { return off.size() - 1; }
+  size_t member_of(size_t t) const { return (size_t)(std::upper_bound(text.begin(), text.end(), t) - text.begin()) - 1; }   // t below the text's size
+  // members [lo, hi) inflated behind out; a member that does not inflate to what its trailer says ends the run, as on the host path
+  void inflate_members(size_t lo, size_t hi, std::vector<char> &out) const {
+    z_stream zs;
+    memset(&zs, 0, sizeof(zs));
+    if (inflateInit2(&zs, -15) != Z_OK) { print_log("ERROR: zlib inflateInit2 failed"); exit(EXIT_FAILURE); }
+    for (size_t m = lo; m < hi; ++m) {
+      const uint8_t *b = base + off[m];
+      const size_t bs = off[m + 1] - off[m], hdr = 12 + ((size_t)b[10] | ((size_t)b[11] << 8)), isize = text[m + 1] - text[m], at = out.size();
+      const uint8_t *tail = b + bs - 8;
+      const uint32_t crc = (uint32_t)tail[0] | ((uint32_t)tail[1] << 8) | ((uint32_t)tail[2] << 16) | ((uint32_t)tail[3] << 24);
+      out.resize(at + isize);
+      inflateReset(&zs);
+      zs.next_in = const_cast<Bytef *>(b + hdr);
+      zs.avail_in = (uInt)(bs - hdr - 8);
+      zs.next_out = (Bytef *)out.data() + at;
+      zs.avail_out = (uInt)isize;
+      const int rc = isize || zs.avail_in > 2 ? inflate(&zs, Z_FINISH) : Z_STREAM_END;
+      if ((rc != Z_STREAM_END && !(rc == Z_OK && zs.avail_out == 0)) || zs.total_out != isize ||
+          (uint32_t)crc32(crc32(0L, Z_NULL, 0), (const Bytef *)out.data() + at, (uInt)isize) != crc) bad_member(off[m]);
+    }
+    inflateEnd(&zs);
+  }
+  void bad_member(size_t at) const {
+    print_log("ERROR: %s: a BGZF block at byte %lu does not inflate to what its trailer says", path.c_str(), (unsigned long)at);
+    exit(EXIT_FAILURE);
+  }
+  // the first verified record start behind the first line end of member m's text, as a text offset;
+  // text.back(): none within kScoutBytes
+  size_t scout(size_t m, std::vector<char> &win) const {
+    win.clear();
+    for (size_t hi = m; hi < members();) {
+      inflate_members(hi, hi + 1, win);
+      ++hi;
+      const bool whole = hi == members();
+      const size_t at = win.empty() ? 0 : resync_text(win.data(), win.size(), fmt, 1, whole);
+      if (at < win.size()) return text[m] + at;
+      if (win.size() >= kScoutBytes) break;
+    }
+    return text.back();
+  }
+  // false: the text does not begin with a record the cutter verifies.  piece_records: records a piece should hold
+  bool plan(size_t piece_records) {
+    std::vector<char> win;
+    const size_t total = text.back();
+    cut.clear();
+    if (total == 0) { cut.assign(2, 0); return true; }
+    // the first record must verify at the text's first byte; bytes per record from it, as the plain files' cutter takes them
+    size_t rec_bytes = 0;
+    bool found = false;
+    for (size_t hi = 0; hi < members() && !found;) {
+      inflate_members(hi, hi + 1, win);
+      ++hi;
+      if (win.empty()) continue;
+      if (!fmt) fmt = win[0];
+      if (fmt != '@' && fmt != '>') return false;
+      const bool whole = hi == members();
+      const size_t first = resync_text(win.data(), win.size(), fmt, 0, whole);
+      if (first != 0 && first < win.size()) return false;
+      if (first == 0) {
+        const size_t second = resync_text(win.data(), win.size(), fmt, 1, whole);
+        if (second < win.size() || whole) { rec_bytes = second; found = true; }
+      }
+      if (!found && win.size() >= kScoutBytes) return false;
+    }
+    if (!found) return false;
+    const size_t piece = std::max<size_t>(16, rec_bytes) * std::max<size_t>(piece_records, 1);
+    cut.push_back(0);
+    for (size_t from = 0;;) {
+      const size_t want = from + piece;
+      if (want >= total) break;
+      size_t m = member_of(want);
+      if (text[m] < want) ++m;                        // the first member that begins at or behind the wanted offset: the floor is one member
+      if (m >= members()) break;
+      const size_t c = scout(m, win);
+      from = want;
+      if (c >= total) continue;                       // no start found within the bound: the boundary is dropped, two pieces become one
+      if (c > cut.back()) { cut.push_back(c); from = c; }
+    }
+    cut.push_back(total);
+    return true;
+  }
+};
 
 // Cuts at given RECORD numbers (pairs: both mate files must be cut at the same record, an interleaved file at an even one).
 // The structure has to be regular for that - 4-line FASTQ (record r starts at line 4 r), or FASTA where every record starts
@@ -600,9 +745,14 @@ struct Batch {
   bool raw = false;
   const char *raw1 = nullptr, *raw2 = nullptr;
   size_t raw1_len = 0, raw2_len = 0, raw_want = 0, raw_first = 0;
+  // --gpu-inflate: raw1 / raw1_len are whole BGZF members of bgzf (a file of the run); the piece is the z_len bytes from byte z_skip
+  // of their text, with no record count fixed in advance; z_off: where the members stand in the file
+  const struct BgzfFile *bgzf = nullptr;
+  size_t z_skip = 0, z_len = 0, z_off = 0, z_m0 = 0, z_m1 = 0;     // (z_m0, z_m1: the members, [first, behind the last))
+  std::vector<char> z_text;            // ... inflated on the host, when the piece takes the host parsers
   const char *id(size_t i) const { return ids.data() + id_off[i]; }
   void reset(bool pair) {   // keeps every buffer's capacity: batches are recycled, so steady state allocates (and page-faults) nothing
-    n = 0; done = false; tsv_device = false; dump_device = false; raw = false; raw1 = raw2 = nullptr; raw1_len = raw2_len = raw_want = raw_first = 0;
+    n = 0; done = false; tsv_device = false; dump_device = false; raw = false; raw1 = raw2 = nullptr; raw1_len = raw2_len = raw_want = raw_first = 0; bgzf = nullptr; z_skip = z_len = z_off = z_m0 = z_m1 = 0;
     ids.clear(); id_off.clear(); qual1.clear(); qual2.clear(); q1_off.clear(); q2_off.clear(); has_qual.clear(); has_qual2.clear();
     bases1.clear(); bases2.clear(); offs1.clear(); offs2.clear(); n_parts = 0;
     bc_raw.clear(); um_raw.clear(); bc_rawq.clear(); um_rawq.clear(); bc_cm.clear(); um_cm.clear(); r1_cm.clear();

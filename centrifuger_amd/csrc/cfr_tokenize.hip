@@ -14,6 +14,8 @@
 //   k_tok_gather    one wave per unit: its sequence bytes to the flat buffer, 64 consecutive bytes per step (a lane per read would be
 //                   64 uncoalesced streams).  A unit has any length: the wave walks it.
 //   k_tok_offsets   one lane per record: the 64-bit offsets of the delivered records; lane 0 writes the summary the host reads back.
+//   k_tok_id_len, k_tok_ids   cfr_tokenizer_fetch_ids: the delivered records' id lengths, (ExclusiveSum), 16 lanes per record copy its id.
+// cfr_tokenize_resident takes the text from this device's memory: one device-to-device copy into the same padded buffer, then the same kernels.
 // No kernel waits for another block: the scans are launches of their own.  No lane keeps an array.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -21,6 +23,8 @@
 #include <algorithm>
 #include <climits>
 #include <cstring>
+#include <stdexcept>
+#include <vector>
 
 #include "cfr_hip_util.hpp"
 #include "cfr_tokenize_core.hpp"
@@ -157,6 +161,22 @@ __global__ __launch_bounds__(kBlock) void k_tok_offsets(TokTables t, uint32_t n_
   if (r == 0) *summary = s;
 }
 
+// the ids of the delivered records (cfr_tokenizer_fetch_ids): lanes 0 .. n write the lengths, the last one the zero the scan ends on
+__global__ __launch_bounds__(kBlock) void k_tok_id_len(const cfr_read_record *records, uint64_t n, uint32_t *len) {
+  const uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (r <= n) len[r] = r == n ? 0u : records[r].id_len;
+}
+// kIdLanes lanes per record copy its id (the id_len bytes behind the header character) to its place
+constexpr int kIdLanes = 16;
+__global__ __launch_bounds__(kBlock) void k_tok_ids(const uint8_t *text, const cfr_read_record *records, uint64_t n, const uint32_t *off, uint8_t *ids) {
+  const uint64_t r = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) / kIdLanes;
+  if (r >= n) return;
+  const uint8_t *src = text + records[r].header + 1;
+  uint8_t *dst = ids + off[r];
+  const uint32_t len = records[r].id_len;
+  for (uint32_t i = threadIdx.x & (kIdLanes - 1); i < len; i += kIdLanes) dst[i] = src[i];
+}
+
 template <class T> void grow(DevBuf<T> &b, size_t &cap, size_t need) {      // by doubling; the old contents are not kept
   if (need <= cap) return;
   const size_t c = std::max(need, cap * 2);
@@ -192,6 +212,76 @@ class TokenizerDevice : public Tokenizer {
     if (len) info->fastq = text[0] == '@';
     bool virtual_newline = false;
     const uint64_t eff = tok_effective_len(text, len, final, virtual_newline);
+    run(text, hipMemcpyHostToDevice, len, eff, virtual_newline, final, max_records, info);
+  }
+
+  // the same with the text in this device's memory: the first byte, and the last one (final) or the last '\n' (looked for from the
+  // end in pieces of kEdge bytes), come to the host to decide what tok_effective_len decides from host text
+  // (text that is to be continued and has no '\n' in its last kEdge bytes costs one small copy and one wait per kEdge bytes until one
+  // is found: len / 65536 round trips at the worst, for a text without any line end - one record of many MB)
+  bool tokenize_resident(const void *d_text, uint64_t len, int final, uint64_t max_records, cfr_token_info *info) override {
+    DeviceScope scope(device_);
+    memset(info, 0, sizeof(*info));
+    n_records_ = 0; total_bases_ = 0; copy_in_ms_ = kernel_ms_ = 0.0;
+    const uint8_t *src = static_cast<const uint8_t *>(d_text);
+    bool virtual_newline = false;
+    uint64_t eff = 0;
+    if (len) {
+      if (!h_edge_) h_edge_.alloc(kEdge);
+      uint8_t *h = h_edge_.get();
+      HIP_CHECK(hipMemcpyAsync(h, src, 1, hipMemcpyDeviceToHost, stream_));
+      HIP_CHECK(hipMemcpyAsync(h + 1, src + len - 1, 1, hipMemcpyDeviceToHost, stream_));
+      HIP_CHECK(hipStreamSynchronize(stream_));
+      if (h[0] != '>' && h[0] != '@') throw std::invalid_argument("cfr_tokenize_resident: the text starts with neither '>' (FASTA) nor '@' (FASTQ)");
+      info->fastq = h[0] == '@';
+      if (final) { virtual_newline = h[1] != '\n'; eff = len + (virtual_newline ? 1 : 0); }
+      else if (h[1] == '\n') eff = len;
+      else
+        for (uint64_t end = len; end > 0 && eff == 0;) {
+          const uint64_t piece = std::min<uint64_t>(end, kEdge), lo = end - piece;
+          HIP_CHECK(hipMemcpyAsync(h, src + lo, piece, hipMemcpyDeviceToHost, stream_));
+          HIP_CHECK(hipStreamSynchronize(stream_));
+          if (const void *nl = memrchr(h, '\n', piece)) eff = lo + (uint64_t)((const uint8_t *)nl - h) + 1;
+          end = lo;
+        }
+    }
+    run(src, hipMemcpyDeviceToDevice, len, eff, virtual_newline, final, max_records, info);
+    return true;
+  }
+
+  bool fetch_ids(char *ids, uint64_t cap, uint64_t *id_off, uint64_t *need) override {
+    DeviceScope scope(device_);
+    const uint64_t n = n_records_;
+    if ((uint64_t)n + 1 > (uint64_t)INT_MAX) throw CapacityError{"cfr_tokenizer_fetch_ids: more than 2^31 - 2 records"};
+    grow(idlen_, cap_idlen_, 2 * ((size_t)n + 1));
+    uint32_t *len = idlen_, *off = len + n + 1;
+    hipLaunchKernelGGL(k_tok_id_len, dim3(grid_for((size_t)n + 1, kBlock)), dim3(kBlock), 0, stream_, (const cfr_read_record *)records_.get(), n, len);
+    HIP_CHECK(hipGetLastError());
+    scan(len, off, (size_t)n + 1);
+    h_idoff_.resize((size_t)n + 1);
+    HIP_CHECK(hipMemcpyAsync(h_idoff_.data(), off, (n + 1) * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    const uint64_t total = h_idoff_[n];
+    *need = total;
+    if (ids && total > cap) return false;
+    if (ids && total) {
+      grow(ids_, cap_ids_, total);
+      hipLaunchKernelGGL(k_tok_ids, dim3(grid_for((size_t)n * kIdLanes, kBlock)), dim3(kBlock), 0, stream_, (const uint8_t *)text_.get(),
+                         (const cfr_read_record *)records_.get(), n, (const uint32_t *)off, ids_.get());
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipMemcpyAsync(ids, ids_, total, hipMemcpyDeviceToHost, stream_));
+      HIP_CHECK(hipStreamSynchronize(stream_));
+    }
+    if (id_off)
+      for (uint64_t r = 0; r <= n; ++r) id_off[r] = h_idoff_[r];
+    return true;
+  }
+
+ private:
+  static constexpr uint64_t kEdge = 1u << 16;
+
+  // src: len bytes of host or device memory (kind says which); eff and virtual_newline as tok_effective_len gives them
+  void run(const uint8_t *text, hipMemcpyKind kind, uint64_t len, uint64_t eff, bool virtual_newline, int final, uint64_t max_records, cfr_token_info *info) {
     HIP_CHECK(hipEventRecord(ev_[0], stream_));
     if (eff == 0) {
       HIP_CHECK(hipMemsetAsync(offsets_, 0, 8, stream_));
@@ -202,7 +292,7 @@ class TokenizerDevice : public Tokenizer {
     const uint64_t padded = (eff + kLaneBytes - 1) / kLaneBytes * kLaneBytes, copied = std::min(len, eff);
     grow(text_, cap_text_, padded);
     grow(bases_, cap_bases_, eff);
-    HIP_CHECK(hipMemcpyAsync(text_, text, copied, hipMemcpyHostToDevice, stream_));
+    HIP_CHECK(hipMemcpyAsync(text_, text, copied, kind, stream_));
     if (padded > copied) HIP_CHECK(hipMemsetAsync(text_.get() + copied, 0, padded - copied, stream_));
     if (virtual_newline) HIP_CHECK(hipMemsetAsync(text_.get() + len, '\n', 1, stream_));
     HIP_CHECK(hipEventRecord(ev_[1], stream_));
@@ -264,6 +354,7 @@ class TokenizerDevice : public Tokenizer {
     n_records_ = h_sum->n_records; total_bases_ = h_sum->total_bases;
   }
 
+ public:
   void fetch(cfr_read_record *records, uint64_t *offsets, uint8_t *bases) override {
     DeviceScope scope(device_);
     if (records && n_records_) HIP_CHECK(hipMemcpyAsync(records, records_, n_records_ * sizeof(cfr_read_record), hipMemcpyDeviceToHost, stream_));
@@ -304,6 +395,11 @@ class TokenizerDevice : public Tokenizer {
   DevBuf<uint64_t> offsets_;
   DevBuf<TokSummary> d_summary_;
   PinnedBuf<uint64_t> h_back_;     // [0]: the two totals; [2..]: the summary
+  PinnedBuf<uint8_t> h_edge_;      // tokenize_resident: the text's first and last byte, or a piece of its end
+  DevBuf<uint32_t> idlen_;         // fetch_ids: the ids' lengths, then their exclusive sum
+  DevBuf<uint8_t> ids_;
+  std::vector<uint32_t> h_idoff_;
+  size_t cap_idlen_ = 0, cap_ids_ = 0;
   size_t cap_text_ = 0, cap_bases_ = 0, cap_tmp_ = 0, cap_blk_ = 0, cap_lines_ = 0, cap_fasta_ = 0, cap_units_ = 0, cap_records_ = 0, cap_offsets_ = 0;
   uint64_t n_records_ = 0, total_bases_ = 0;
   double copy_in_ms_ = 0.0, kernel_ms_ = 0.0;

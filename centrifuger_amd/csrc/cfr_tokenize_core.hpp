@@ -157,6 +157,12 @@ class Tokenizer {
   virtual bool device_reads(const void **d_bases, const void **d_offsets) { (void)d_bases; (void)d_offsets; return false; }
   // the text and the record table of the last call in HBM (the id of record r: id_len bytes at text + header + 1); false on the host twin
   virtual bool device_records(const void **d_text, const void **d_records) { (void)d_text; (void)d_records; return false; }
+  // tokenize with the text in the handle's own device memory (copied device to device into the handle's buffer); false on the host twin
+  virtual bool tokenize_resident(const void *d_text, uint64_t len, int final, uint64_t max_records, cfr_token_info *info) {
+    (void)d_text; (void)len; (void)final; (void)max_records; (void)info; return false;
+  }
+  // the ids of the last call's records back to back, and n_records + 1 offsets; false: the ids take *need bytes, more than cap
+  virtual bool fetch_ids(char *ids, uint64_t cap, uint64_t *id_off, uint64_t *need) = 0;
 };
 Tokenizer *make_tokenizer_host();                 // cfr_tokenize_host.cpp
 Tokenizer *make_tokenizer_device(int device);     // cfr_tokenize.hip; throws HipError{.., -1} without that GPU

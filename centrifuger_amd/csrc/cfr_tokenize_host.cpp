@@ -15,7 +15,7 @@ class TokenizerHost : public Tokenizer {
  public:
   void tokenize(const uint8_t *text, uint64_t len, int final, uint64_t max_records, cfr_token_info *info) override {
     const auto t0 = std::chrono::steady_clock::now();
-    records_.clear(); offsets_.assign(1, 0); bases_.clear();
+    records_.clear(); offsets_.assign(1, 0); bases_.clear(); ids_.clear(); id_off_.assign(1, 0);
     memset(info, 0, sizeof(*info));
     if (len == 0) return;
     info->fastq = text[0] == '@';
@@ -65,6 +65,12 @@ class TokenizerHost : public Tokenizer {
     const uint32_t u_end = t.fastq ? (uint32_t)s.n_records : (s.n_records < t.H ? t.hdr_line[s.n_records] : t.L);
     for (uint32_t u = 0; u < u_end; ++u)
       if (weight_[u]) memcpy(bases_.data() + dst_[u], text + t.lstart[t.fastq ? 4 * u + 1 : u], weight_[u]);
+    id_off_.resize(s.n_records + 1);                        // the ids are kept: the caller's text may be gone when they are asked for
+    for (uint32_t r = 0; r < s.n_records; ++r) {
+      const uint8_t *id = text + records_[r].header + 1;
+      ids_.insert(ids_.end(), id, id + records_[r].id_len);
+      id_off_[r + 1] = ids_.size();
+    }
     info->device_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
 
@@ -74,11 +80,19 @@ class TokenizerHost : public Tokenizer {
     if (bases && !bases_.empty()) memcpy(bases, bases_.data(), bases_.size());
   }
 
+  bool fetch_ids(char *ids, uint64_t cap, uint64_t *id_off, uint64_t *need) override {
+    *need = ids_.size();
+    if (ids && ids_.size() > cap) return false;
+    if (ids && !ids_.empty()) memcpy(ids, ids_.data(), ids_.size());
+    if (id_off) memcpy(id_off, id_off_.data(), id_off_.size() * 8);
+    return true;
+  }
+
  private:
   std::vector<uint32_t> lstart_, lcend_, hdr_line_, line_rec_, weight_, dst_;
   std::vector<cfr_read_record> records_;
-  std::vector<uint64_t> offsets_;
-  std::vector<uint8_t> bases_;
+  std::vector<uint64_t> offsets_, id_off_;
+  std::vector<uint8_t> bases_, ids_;
 };
 
 }  // namespace

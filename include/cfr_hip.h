@@ -654,6 +654,54 @@ void cfr_gz_eof(const uint8_t **bytes, size_t *n);
 cfr_status cfr_gz_get_stats(cfr_gz *h, cfr_gz_stats *st);
 void cfr_gz_close(cfr_gz *h);
 
+/* ---- BGZF members back into text (the inverse of cfr_gz_compress: any BGZF, not only this library's; the framing, the decoder
+ * and the statuses are stated in csrc/cfr_inflate_core.hpp) ----
+ * cfr_inflate_open: device >= 0: the kernel of cfr_inflate.hip on that GPU (CFR_ERR_NO_DEVICE without it: no fall-back);
+ *   device = -1: the host twin (no zlib call), the same text and statuses.
+ * cfr_inflate_bgzf: `members` is n bytes of whole BGZF members back to back.  Bytes that are no BGZF header where one is due:
+ *   CFR_ERR_ARG, nothing is launched.  A member that frames but does not inflate to what its trailer says is CFR_OK: it is counted
+ *   in info->bad_members (first_bad: its index, first_bad_status: why), its ISIZE bytes of the text are zero, the other members are
+ *   not touched - the caller decides.  n = 0: CFR_OK and no text.  4 GiB of text or more in one call: CFR_ERR_ARG.
+ *   fetch_text != 0: *text points at the text in a buffer the handle owns until its next call; fetch_text = 0 on a device handle:
+ *   the text stays in HBM (cfr_inflate_device_text) and *text is NULL.  *text_n is the text's size either way.
+ * cfr_inflate_member_status: the last call's members: status[i] (a cfr_inflate_member_code) for i < members and
+ *   text_off[i] for i <= members, the exclusive sum of the members' text sizes; either pointer may be NULL; cap = the entries
+ *   status holds (text_off: cap + 1), CFR_ERR_CAPACITY when the call had more members.
+ * cfr_inflate_device_text: device handle only (CFR_ERR_ARG on the host twin): the last call's text in HBM; valid until the next
+ *   call or close on the handle.
+ * cfr_inflate_get_stats: device times of the last call from events (the host twin: wall time in inflate_ms).
+ * A handle is used by one thread at a time. */
+typedef struct cfr_inflate cfr_inflate;
+typedef enum {
+  CFR_INF_OK = 0,
+  CFR_INF_BAD_HEADER = 1,      /* ISIZE above 65536, or whole bytes between the deflate stream and the trailer */
+  CFR_INF_BAD_BLOCK_TYPE = 2,  /* BTYPE 11 */
+  CFR_INF_BAD_STORED_LEN = 3,  /* LEN is not the complement of NLEN */
+  CFR_INF_BAD_CODE_SET = 4,    /* over-subscribed or incomplete lengths, too many symbols, a bad repeat, no end-of-block code */
+  CFR_INF_BAD_SYMBOL = 5,      /* a code no symbol has, length symbol 286 / 287, distance symbol 30 / 31, a distance in front of the member */
+  CFR_INF_INPUT = 6,           /* the stream ends inside a block */
+  CFR_INF_OUTPUT_LONG = 7,     /* more text than ISIZE */
+  CFR_INF_OUTPUT_SHORT = 8,    /* less text than ISIZE */
+  CFR_INF_BAD_CRC = 9
+} cfr_inflate_member_code;
+typedef struct { uint64_t members, bad_members, first_bad, bytes_in, bytes_out; int32_t first_bad_status; } cfr_inflate_info;
+typedef struct { float upload_ms, inflate_ms, download_ms; } cfr_inflate_stats;
+cfr_status cfr_inflate_open(int device, cfr_inflate **out);
+cfr_status cfr_inflate_bgzf(cfr_inflate *h, const uint8_t *members, uint64_t n, int fetch_text,
+                            const uint8_t **text, uint64_t *text_n, cfr_inflate_info *info);
+cfr_status cfr_inflate_member_status(cfr_inflate *h, uint8_t *status, uint64_t *text_off, uint64_t cap);
+cfr_status cfr_inflate_device_text(cfr_inflate *h, const void **d_text, uint64_t *n);
+cfr_status cfr_inflate_get_stats(cfr_inflate *h, cfr_inflate_stats *st);
+void cfr_inflate_close(cfr_inflate *h);
+/* cfr_tokenize_resident: cfr_tokenize with its source in the memory of the tokeniser's own device (cfr_inflate_device_text, or a
+ *   range inside it): one device-to-device copy into the tokeniser's padded buffer, then everything as in cfr_tokenize - the same
+ *   rules, limits and results.  CFR_ERR_ARG on the host twin.
+ * cfr_tokenizer_fetch_ids: the ids of the last call's records back to back without terminators, and n_records + 1 offsets
+ *   (either pointer may be NULL).  ids_cap below the ids' bytes: CFR_ERR_CAPACITY (no id is longer than its header line, so the
+ *   text's length is always enough).  On the device a gather kernel and one copy; the host twin has kept them. */
+cfr_status cfr_tokenize_resident(cfr_tokenizer *t, const void *d_text, uint64_t len, int final, uint64_t max_records, cfr_token_info *info);
+cfr_status cfr_tokenizer_fetch_ids(cfr_tokenizer *t, char *ids, uint64_t ids_cap, uint64_t *id_off);
+
 /* ---- single-cell input: read formats, barcode whitelist, barcode translation (ReadFormatter.hpp, BarcodeCorrector.hpp,
  * BarcodeTranslator.hpp; the flow of CentrifugerClass.cpp:163-224, :565-574) ----
  * Handles of their own, independent of any cfr_dev_index; one call at a time per handle.  Barcodes, reads and comments are flat
