@@ -114,6 +114,8 @@ EXPORTS = [
     "cfr_gz_options_default", "cfr_gz_open", "cfr_gz_compress", "cfr_gz_dump", "cfr_gz_eof", "cfr_gz_get_stats", "cfr_gz_close",
     "cfr_inflate_open", "cfr_inflate_bgzf", "cfr_inflate_member_status", "cfr_inflate_device_text", "cfr_inflate_get_stats", "cfr_inflate_close",
     "cfr_tokenize_resident", "cfr_tokenizer_fetch_ids",
+    "cfr_refseq_open", "cfr_refseq_feed", "cfr_refseq_fetch", "cfr_refseq_assemble", "cfr_refseq_text", "cfr_refseq_get_stats", "cfr_refseq_close",
+    "cfr_build_select", "cfr_build_selection_get", "cfr_build_selection_free", "cfr_file_base_name", "cfr_build_index_assembled",
 ]
 
 _lib = None
@@ -141,7 +143,8 @@ def lib():
                             "cfr_barcode_translate_destroy", "cfr_tsv_header_ex", "cfr_format_tsv_ex",
                             "cfr_taxonomy_tax_name", "cfr_taxonomy_seq_name", "cfr_tax_rank_string", "cfr_taxonomy_close",
                             "cfr_tokenizer_close", "cfr_kreport_options_default", "cfr_tsv_options_default", "cfr_tsv_close",
-                            "cfr_gz_options_default", "cfr_gz_eof", "cfr_gz_close", "cfr_inflate_close"):
+                            "cfr_gz_options_default", "cfr_gz_eof", "cfr_gz_close", "cfr_inflate_close", "cfr_refseq_close",
+                            "cfr_build_selection_free", "cfr_file_base_name"):
                 getattr(L, name).restype = C.c_int
         for name in ("cfr_quant_destroy", "cfr_read_format_destroy", "cfr_barcode_destroy", "cfr_barcode_translate_destroy"):
             getattr(L, name).restype = None
@@ -166,6 +169,11 @@ def lib():
         L.cfr_gz_eof.restype = None
         L.cfr_inflate_close.restype = None
         L.cfr_inflate_close.argtypes = [C.c_void_p]
+        for name in ("cfr_refseq_close", "cfr_build_selection_free"):
+            getattr(L, name).restype = None
+            getattr(L, name).argtypes = [C.c_void_p]
+        L.cfr_file_base_name.restype = C.c_size_t
+        L.cfr_file_base_name.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t]
         _lib = L
     return _lib
 
@@ -200,7 +208,7 @@ class BuildInput(C.Structure):
                 ("text", C.c_void_p), ("n_nodes", C.c_uint64), ("node_taxid", C.c_void_p), ("node_parent", C.c_void_p),
                 ("node_rank", C.POINTER(C.c_char_p)), ("n_names", C.c_uint64), ("name_taxid", C.c_void_p), ("name_text", C.POINTER(C.c_char_p)),
                 ("n_genomes", C.c_uint64), ("genome_seq", C.c_void_p), ("genome_lens", C.c_void_p), ("n_extra", C.c_uint64),
-                ("n_present_taxids", C.c_uint64), ("present_taxids", C.c_void_p)]
+                ("n_present_taxids", C.c_uint64), ("present_taxids", C.c_void_p), ("selection", C.c_void_p)]
 
 
 class BuildOptions(C.Structure):
@@ -250,6 +258,175 @@ def build_index(names, taxids, seqs, nodes, tax_names, out_prefix, ftab_chars=10
     opt.protein = int(protein)
     rep = BuildReport()
     _check(lib().cfr_build_index(C.byref(inp), C.byref(opt), out_prefix.encode(), C.byref(rep)))
+    return {"n": rep.n, "b": rep.block_size, "first_isa": rep.first_isa, "seconds_sa": rep.seconds_sa, "seconds_total": rep.seconds_total,
+            "rounds": rep.rounds}
+
+
+# ---- the reference text of the index writer (cfr_refseq_*, cfr_build_select, cfr_build_index_assembled) ----
+REFSEQ_RECORD_DTYPE = np.dtype([("header", "<u4"), ("header_len", "<u4"), ("id_len", "<u4"), ("kept", "<u4")])
+REFSEQ_SEGMENT_DTYPE = np.dtype([("src", "<u8"), ("len", "<u8"), ("dst", "<u8")])
+
+
+class RefseqInfo(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("consumed", C.c_uint64), ("lead_kept", C.c_uint64), ("kept", C.c_uint64), ("u_start", C.c_uint64),
+                ("at_line_start", C.c_int32), ("pad", C.c_int32), ("device_ms", C.c_double)]
+
+
+class RefseqStats(C.Structure):
+    _fields_ = [("feed_ms", C.c_double), ("copy_in_ms", C.c_double), ("assemble_ms", C.c_double)]
+
+
+class SelectRecord(C.Structure):
+    _fields_ = [("id", C.c_char_p), ("file", C.c_char_p), ("first_piece", C.c_uint64), ("n_pieces", C.c_uint64)]
+
+
+class SelectOptions(C.Structure):
+    _fields_ = [("file_level", C.c_int32), ("concat_tax_genome", C.c_int32), ("ignore_uncategorized", C.c_int32), ("protein", C.c_int32),
+                ("subset_tax", C.c_uint64), ("ftab_chars", C.c_int32), ("pad", C.c_int32)]
+
+
+def file_base_name(path: str) -> str:
+    """cfr_file_base_name: Utils::GetFileBaseName(path, "fna|fa|fasta|faa")"""
+    buf = C.create_string_buffer(len(path.encode()) + 1)
+    lib().cfr_file_base_name(path.encode(), buf, C.c_size_t(len(buf)))
+    return buf.value.decode()
+
+
+class Refseq:
+    """cfr_refseq: the bytes of reference FASTA files -> records and the stream U of kept symbols; assemble() copies segments of U into
+    the text T of the index.  device=None: the host twin, no GPU is touched (the only path with protein=True)."""
+
+    def __init__(self, device=None, protein=False):
+        self._h = C.c_void_p()
+        self._last = RefseqInfo()
+        self._n = 0
+        _check(lib().cfr_refseq_open(C.c_int(-1 if device is None else device), C.c_int(int(bool(protein))), C.byref(self._h)))
+
+    def feed(self, text, at_line_start=True, final=True) -> RefseqInfo:
+        a = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else _u8(text)
+        info = RefseqInfo()
+        _check(lib().cfr_refseq_feed(self._h, _p(a), C.c_uint64(len(a)), C.c_int(int(bool(at_line_start))), C.c_int(int(bool(final))), C.byref(info)))
+        self._last = info
+        return info
+
+    def fetch(self):
+        """-> REFSEQ_RECORD_DTYPE[n_records] of the last feed()"""
+        rec = np.zeros(self._last.n_records, dtype=REFSEQ_RECORD_DTYPE)
+        _check(lib().cfr_refseq_fetch(self._h, _p(rec)))
+        return rec
+
+    def feed_file(self, data: bytes, chunk: int):
+        """The bytes of one file in chunks of `chunk` bytes, as the command line feeds them -> [(id, [(src, len), ...]), ...]: every record
+        with the pieces of U that hold its kept symbols (symbols before a file's first header belong to no record)."""
+        out, at, line_start = [], 0, True
+        while True:
+            piece = data[at:at + chunk]
+            final = at + chunk >= len(data)
+            info = self.feed(piece, line_start, final)
+            recs = self.fetch()
+            src = info.u_start
+            if info.lead_kept and out:
+                out[-1][1].append((src, int(info.lead_kept)))
+            src += info.lead_kept
+            for r in recs:
+                h = int(r["header"])
+                out.append((bytes(piece[h + 1:h + 1 + int(r["id_len"])]).decode("latin-1"), [(src, int(r["kept"]))] if r["kept"] else []))
+                src += int(r["kept"])
+            at += info.consumed
+            line_start = bool(info.at_line_start)
+            if final:
+                return out
+
+    def assemble(self, segments, n=None):
+        """segments: REFSEQ_SEGMENT_DTYPE array or a list of (src, len, dst)"""
+        seg = np.ascontiguousarray(np.array(segments, dtype=REFSEQ_SEGMENT_DTYPE) if not isinstance(segments, np.ndarray) else segments)
+        if n is None:
+            n = int(seg["len"].sum())
+        _check(lib().cfr_refseq_assemble(self._h, _p(seg), C.c_uint64(len(seg)), C.c_uint64(n)))
+        self._n = n
+
+    def text(self) -> bytes:
+        out = np.zeros(max(self._n, 1), dtype=np.uint8)
+        _check(lib().cfr_refseq_text(self._h, _p(out)))
+        return out[:self._n].tobytes()
+
+    def stats(self) -> RefseqStats:
+        st = RefseqStats()
+        _check(lib().cfr_refseq_get_stats(self._h, C.byref(st)))
+        return st
+
+    def close(self):
+        if self._h:
+            lib().cfr_refseq_close(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _build_input(names, taxids, nodes, tax_names, present_taxids=None):
+    def strs(items):
+        arr = (C.c_char_p * max(len(items), 1))()
+        arr[:len(items)] = [x.encode() if isinstance(x, str) else x for x in items]
+        return arr
+    inp = BuildInput()
+    keep = [strs(list(names)), _u64(np.array(taxids, dtype=np.uint64)),
+            _u64(np.array([t for t, _, _ in nodes], dtype=np.uint64)), _u64(np.array([p for _, p, _ in nodes], dtype=np.uint64)),
+            strs([r for _, _, r in nodes]), _u64(np.array([t for t, _ in tax_names], dtype=np.uint64)), strs([x for _, x in tax_names]),
+            _u64(np.array(present_taxids if present_taxids is not None else [], dtype=np.uint64))]
+    inp.n_seqs = len(names); inp.seq_names = keep[0]; inp.seq_taxids = _p(keep[1])
+    inp.n_nodes = len(nodes); inp.node_taxid = _p(keep[2]); inp.node_parent = _p(keep[3]); inp.node_rank = keep[4]
+    inp.n_names = len(tax_names); inp.name_taxid = _p(keep[5]); inp.name_text = keep[6]
+    inp.n_present_taxids = len(keep[7]); inp.present_taxids = _p(keep[7])
+    return inp, keep
+
+
+class BuildSelection:
+    """cfr_build_select: records -> genomes and segments.  names / taxids: the conversion table (file_level: the file list, base names);
+    records: [(id, file, [(src, len), ...]), ...] in reading order."""
+
+    def __init__(self, names, taxids, nodes, tax_names, records, ftab_chars=10, file_level=False, concat=False, ignore_uncategorized=False,
+                 subset_tax=0, protein=False, present_taxids=None):
+        self._h = C.c_void_p()
+        self.inp, self._keep = _build_input(names, taxids, nodes, tax_names, present_taxids)
+        recs = (SelectRecord * max(len(records), 1))()
+        pieces = []
+        for k, (rid, f, pcs) in enumerate(records):
+            recs[k].id, recs[k].file, recs[k].first_piece, recs[k].n_pieces = rid.encode("latin-1"), f.encode(), len(pieces), len(pcs)
+            pieces.extend(pcs)
+        pc = np.ascontiguousarray(np.array(pieces, dtype=np.uint64).reshape(-1, 2))
+        so = SelectOptions(int(file_level), int(concat), int(ignore_uncategorized), int(protein), subset_tax, ftab_chars, 0)
+        _check(lib().cfr_build_select(C.byref(self.inp), C.byref(so), recs, C.c_uint64(len(records)), _p(pc), C.c_uint64(len(pc)), C.byref(self._h)))
+        self.inp.selection = self._h
+        seg, ns, n, ng, nx = C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().cfr_build_selection_get(self._h, C.byref(seg), C.byref(ns), C.byref(n), C.byref(ng), C.byref(nx)))
+        self.n, self.n_genomes, self.n_extra = n.value, ng.value, nx.value
+        self.segments = np.ctypeslib.as_array(C.cast(seg, C.POINTER(C.c_uint64)), shape=(ns.value * 3,)).copy().view(REFSEQ_SEGMENT_DTYPE) if ns.value else np.zeros(0, dtype=REFSEQ_SEGMENT_DTYPE)
+
+    def close(self):
+        if self._h:
+            lib().cfr_build_selection_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def build_index_assembled(refseq: Refseq, selection: BuildSelection, out_prefix, ftab_chars=10, offrate=4, rbbwt_b=0, device=0, threads=0, verbose=False,
+                          protein=False):
+    """cfr_build_index_assembled: the writer on the text the handle has assembled from selection.segments"""
+    opt = BuildOptions()
+    lib().cfr_build_options_default(C.byref(opt))
+    opt.ftab_chars, opt.offrate, opt.device, opt.threads, opt.rbbwt_b, opt.verbose = ftab_chars, offrate, device, threads, rbbwt_b, int(verbose)
+    opt.protein = int(protein)
+    rep = BuildReport()
+    _check(lib().cfr_build_index_assembled(refseq._h, C.byref(selection.inp), C.byref(opt), out_prefix.encode(), C.byref(rep)))
     return {"n": rep.n, "b": rep.block_size, "first_isa": rep.first_isa, "seconds_sa": rep.seconds_sa, "seconds_total": rep.seconds_total,
             "rounds": rep.rounds}
 

@@ -16,6 +16,7 @@
 #include <cstring>
 #include <ctime>
 #include <map>
+#include <memory>
 #include <set>
 #include <stdexcept>
 #include <thread>
@@ -194,69 +195,31 @@ const char *kRanks[] = {"no rank", "strain", "species", "genus", "family", "orde
                         "subphylum", "subspecies", "subtribe", "superclass", "superfamily", "superkingdom", "superorder", "superphylum",
                         "tribe", "varietas", "life", "acellular root"};
 
-// Taxonomy::Init + Save (Taxonomy.hpp:146-232, 1238-1257)
-void write_taxonomy(const std::string &path, const BuildInput &in) {
-  std::map<uint64_t, std::pair<uint64_t, int>> tree;            // tax id -> (parent, rank code); first mention wins
-  for (const auto &nd : in.nodes) {
-    if (tree.count(nd.taxid)) continue;
-    int rk = 0;
-    for (size_t k = 0; k < sizeof(kRanks) / sizeof(kRanks[0]); ++k) if (nd.rank == kRanks[k]) { rk = (int)k; break; }
-    tree[nd.taxid] = {nd.parent, rk};
-  }
-  std::set<uint64_t> selected;                                   // the ids on the paths from the sequences' ids to the root
-  std::set<uint64_t> present(in.taxids.begin(), in.taxids.end());
-  present.insert(in.present_taxids.begin(), in.present_taxids.end());
-  for (uint64_t tid : present) {
-    uint64_t p = tid;
-    if (!tree.count(p)) continue;
-    // ReadTaxonomyTree walks with std::map operator[] (Taxonomy.hpp:190-197): a parent the file does not name is default-constructed
-    // on the way - parent 0, rank code 0, no leaf - and so is tax id 0 after it, which is its own parent.  Both phantom nodes are kept
-    // (and a later id of `present` finds them in the tree), so an orphaned subtree gives a forest whose first top is the phantom id 0.
-    while (!selected.count(p)) {
-      selected.insert(p);
-      p = tree[p].first;
-    }
-  }
-  std::vector<uint64_t> order(selected.begin(), selected.end());  // compact ids follow ascending original id (std::map order)
-  std::map<uint64_t, uint64_t> cid;
-  for (size_t i = 0; i < order.size(); ++i) cid[order[i]] = i;
-  std::vector<uint8_t> leaf(order.size(), 1);
-  std::vector<uint64_t> parent_c(order.size());
-  for (size_t i = 0; i < order.size(); ++i) {
-    const uint64_t par = tree[order[i]].first;
-    auto it = cid.find(par);
-    if (it != cid.end()) { parent_c[i] = it->second; leaf[it->second] = 0; }
-    else parent_c[i] = i;
-  }
-  // a root is its own parent, which marked it a non-leaf above exactly like the reference's loop does
-  std::map<uint64_t, std::string> sci;
-  for (const auto &nm : in.tax_names) {
-    if (!cid.count(nm.first)) continue;
-    std::string s;                                               // "_".join(name.split())
-    bool in_word = false;
-    for (char ch : nm.second) {
-      const bool sp = ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r' || ch == '\f' || ch == '\v';
-      if (sp) { in_word = false; continue; }
-      if (!in_word && !s.empty()) s += '_';
-      s += ch;
-      in_word = true;
-    }
-    sci[nm.first] = s;
-  }
+// Taxonomy::Save (Taxonomy.hpp:1238-1257) of the compact taxonomy c
+void write_taxonomy(const std::string &path, const BuildInput &in, const TaxCompact &c) {
+  const size_t nodes = c.order.size();
   Out o(path);
-  o.u64(order.size()); o.u64(in.taxids.size()); o.u64(in.n_extra);          // _nodeCnt, _seqCnt, _extraSeqCnt
-  for (size_t i = 0; i < order.size(); ++i) {
-    o.u64(parent_c[i]);
-    const uint8_t tail[8] = {(uint8_t)tree[order[i]].second, leaf[i], 0, 0, 0, 0, 0, 0};
+  // _nodeCnt, _seqCnt, _extraSeqCnt (SetTaxIdAsSeqId, Taxonomy.hpp:1217-1236: one sequence per node and "uncategorized", no extra names)
+  o.u64(nodes); o.u64(in.taxid_as_seqid ? nodes + 1 : in.taxids.size()); o.u64(in.taxid_as_seqid ? 0 : in.n_extra);
+  for (size_t i = 0; i < nodes; ++i) {
+    o.u64(c.parent[i]);
+    const uint8_t tail[8] = {c.rank[i], c.leaf[i], 0, 0, 0, 0, 0, 0};
     o.raw(tail, 8);
   }
-  o.u64(order.size());
-  for (uint64_t tid : order) o.u64(tid);
-  for (uint64_t tid : order) { const std::string &s = sci[tid]; o.u64(s.size()); o.raw(s.data(), s.size()); }
+  o.u64(nodes);
+  for (uint64_t tid : c.order) o.u64(tid);
+  for (const std::string &s : c.name) { o.u64(s.size()); o.raw(s.data(), s.size()); }
+  if (in.taxid_as_seqid) {
+    for (size_t i = 0; i <= nodes; ++i) o.u64(i);
+    for (const std::string &s : c.name) { o.u64(s.size()); o.raw(s.data(), s.size()); }
+    o.u64(13); o.raw("uncategorized", 13);
+    o.close();
+    return;
+  }
   for (uint64_t tid : in.taxids) {
     // a tax id outside the tree: the reference warns and its MapID::Map (std::map operator[]) hands out compact id 0
-    auto it = cid.find(tid);
-    if (it == cid.end()) { fprintf(stderr, "WARNING: %llu is not in the taxonomy tree\n", (unsigned long long)tid); o.u64(0); }
+    auto it = c.cid.find(tid);
+    if (it == c.cid.end()) { fprintf(stderr, "WARNING: %llu is not in the taxonomy tree\n", (unsigned long long)tid); o.u64(0); }
     else o.u64(it->second);
   }
   for (const std::string &nm : in.names) { o.u64(nm.size()); o.raw(nm.data(), nm.size()); }
@@ -500,7 +463,7 @@ void build_protein_index_files(const BuildInput &in, const BuildOptions &opt, co
     write_fixed_array(o, end_sa);
     o.close();
   }
-  write_taxonomy(prefix + ".2.cfr", in);
+  write_taxonomy(prefix + ".2.cfr", in, *in.compact);
   {
     Out o(prefix + ".3.cfr");
     std::map<uint64_t, uint64_t> by_id;                        // lengths count the '$' (Builder.hpp:143-156: what Compact returned)
@@ -523,7 +486,167 @@ void build_protein_index_files(const BuildInput &in, const BuildOptions &opt, co
 
 }  // namespace
 
-void build_index_files(const BuildInput &in, const BuildOptions &opt, const std::string &prefix, BuildReport *rep) {
+// Taxonomy::Init (Taxonomy.hpp:146-232)
+std::shared_ptr<const TaxCompact> compact_taxonomy(const BuildInput &in) {
+  auto out = std::make_shared<TaxCompact>();
+  TaxCompact &c = *out;
+  std::map<uint64_t, std::pair<uint64_t, int>> tree;            // tax id -> (parent, rank code); first mention wins
+  for (const auto &nd : in.nodes) {
+    if (tree.count(nd.taxid)) continue;
+    int rk = 0;
+    for (size_t k = 0; k < sizeof(kRanks) / sizeof(kRanks[0]); ++k) if (nd.rank == kRanks[k]) { rk = (int)k; break; }
+    tree[nd.taxid] = {nd.parent, rk};
+  }
+  std::set<uint64_t> selected;                                   // the ids on the paths from the sequences' ids to the root
+  std::set<uint64_t> present(in.taxids.begin(), in.taxids.end());
+  present.insert(in.present_taxids.begin(), in.present_taxids.end());
+  for (uint64_t tid : present) {
+    uint64_t p = tid;
+    if (!tree.count(p)) continue;
+    // ReadTaxonomyTree walks with std::map operator[] (Taxonomy.hpp:190-197): a parent the file does not name is default-constructed
+    // on the way - parent 0, rank code 0, no leaf - and so is tax id 0 after it, which is its own parent.  Both phantom nodes are kept
+    // (and a later id of `present` finds them in the tree), so an orphaned subtree gives a forest whose first top is the phantom id 0.
+    while (!selected.count(p)) {
+      selected.insert(p);
+      p = tree[p].first;
+    }
+  }
+  c.order.assign(selected.begin(), selected.end());               // compact ids follow ascending original id (std::map order)
+  for (size_t i = 0; i < c.order.size(); ++i) c.cid[c.order[i]] = i;
+  c.leaf.assign(c.order.size(), 1);
+  c.parent.resize(c.order.size());
+  c.rank.resize(c.order.size());
+  for (size_t i = 0; i < c.order.size(); ++i) {
+    const uint64_t par = tree[c.order[i]].first;
+    c.rank[i] = (uint8_t)tree[c.order[i]].second;
+    auto it = c.cid.find(par);
+    if (it != c.cid.end()) { c.parent[i] = it->second; c.leaf[it->second] = 0; }
+    else c.parent[i] = i;
+  }
+  // a root is its own parent, which marked it a non-leaf above exactly like the reference's loop does
+  c.name.assign(c.order.size(), std::string());
+  for (const auto &nm : in.tax_names) {
+    auto at = c.cid.find(nm.first);
+    if (at == c.cid.end()) continue;
+    std::string s;                                               // "_".join(name.split())
+    bool in_word = false;
+    for (char ch : nm.second) {
+      const bool sp = ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r' || ch == '\f' || ch == '\v';
+      if (sp) { in_word = false; continue; }
+      if (!in_word && !s.empty()) s += '_';
+      s += ch;
+      in_word = true;
+    }
+    c.name[at->second] = s;
+  }
+  return out;
+}
+
+std::string file_base_name(const std::string &path) {
+  const size_t slash = path.find_last_of('/');
+  std::string b = slash == std::string::npos ? path : path.substr(slash + 1);
+  const size_t dot = b.find_last_of('.');
+  if (dot != std::string::npos) b.resize(dot);
+  for (const char *ext : {".fna", ".fa", ".fasta", ".faa"}) {
+    const size_t k = strlen(ext);
+    if (b.size() >= k && b.compare(b.size() - k, k, ext) == 0) { b.resize(b.size() - k); break; }
+  }
+  return b;
+}
+
+void select_genomes(BuildInput &in, const SelectOptions &so, const std::vector<SelectRecord> &records, std::vector<SelectSegment> &segments, uint64_t &n) {
+  if (so.protein && (so.file_level || so.concat))
+    throw std::runtime_error("index build: --protein with a two-column file list or with --concat-tax-genome is outside this writer (the reference closes every record with '$' there)");
+  if (!in.compact) in.compact = compact_taxonomy(in);
+  const TaxCompact &c = *in.compact;
+  const uint64_t node_cnt = c.order.size(), n_table = in.taxids.size();
+  if (in.names.size() != n_table) throw std::invalid_argument("index build: the selection starts from the conversion table's names alone");
+  // Taxonomy::SeqIdToTaxId (Taxonomy.hpp:718-724): the compact tax id of a listed sequence (0 for an id outside the tree), _nodeCnt for any other
+  auto seq_ctax = [&](uint64_t seqid) -> uint64_t {
+    if (seqid >= n_table) return node_cnt;
+    auto it = c.cid.find(in.taxids[seqid]);
+    return it == c.cid.end() ? 0 : it->second;
+  };
+  // Taxonomy::GetChildrenTax (Taxonomy.hpp:1038-1082): the compact ids whose way to their top passes the subset's node, itself included
+  std::vector<uint8_t> under;
+  if (so.subset_tax) {
+    under.assign(node_cnt + 1, 0);
+    auto it = c.cid.find(so.subset_tax);
+    if (it != c.cid.end()) {
+      std::vector<int8_t> seen(node_cnt, -1);
+      seen[it->second] = 1;
+      std::vector<uint64_t> path;
+      for (uint64_t i = 0; i < node_cnt; ++i) {
+        uint64_t t = i;
+        path.clear();
+        while (t != c.parent[t] && seen[t] == -1) { path.push_back(t); t = c.parent[t]; }
+        const int8_t res = seen[t] == -1 ? 0 : seen[t];
+        for (uint64_t q : path) seen[q] = res;
+      }
+      for (uint64_t i = 0; i < node_cnt; ++i) under[i] = seen[i] == 1;
+    }
+  }
+  std::map<std::string, uint64_t> seq_index;
+  for (uint64_t i = 0; i < in.names.size(); ++i) seq_index.emplace(in.names[i], i);
+  std::vector<char> taken(in.names.size(), 0);           // per sequence id: a record with this id is already part of the text (_seqLength)
+  std::map<uint64_t, std::vector<SelectPiece>> groups;   // --concat-tax-genome: the pieces of every compact tax id, in record order
+  in.genome_seq.clear(); in.lens.clear(); in.n_extra = 0;
+  segments.clear();
+  n = 0;
+  auto place = [&](const std::vector<SelectPiece> &pieces) {
+    for (const SelectPiece &p : pieces) {
+      if (!p.len) continue;
+      if (!segments.empty() && segments.back().src + segments.back().len == p.src) segments.back().len += p.len;
+      else segments.push_back(SelectSegment{p.src, p.len, n});
+      n += p.len;
+    }
+  };
+  for (const SelectRecord &rec : records) {
+    const std::string name = so.file_level ? file_base_name(rec.file) : rec.id;
+    auto it = seq_index.find(name);
+    uint64_t seqid = it == seq_index.end() ? in.names.size() : it->second;
+    if (so.subset_tax && !under[seq_ctax(seqid)]) continue;                    // (before every other rule; a record without a tax id goes silently)
+    if (!so.file_level && it != seq_index.end() && taken[seqid]) continue;     // a repeated sequence id is stored once (Builder.hpp:129-130)
+    if (it == seq_index.end()) {
+      fprintf(stderr, "WARNING: taxonomy id doesn't exist for %s!\n", name.c_str());
+      if (so.ignore_uncategorized) continue;
+      seq_index.emplace(name, seqid);                                          // Taxonomy::AddExtraSeqName: a new id behind the table's, no tax id
+      in.names.push_back(name);
+      taken.push_back(0);
+      ++in.n_extra;
+    }
+    uint64_t len = 0;
+    for (const SelectPiece &p : rec.pieces) len += p.len;
+    if (len + (so.protein ? 1 : 0) < (uint64_t)so.ftab_chars + 1) {            // a genome too short (Builder.hpp:143-150; a protein's '$' counts): filtered, and its id is not taken
+      fprintf(stderr, "WARNING: %s is filtered due to its short length (could be from masker)!\n", rec.id.c_str());
+      continue;
+    }
+    if (so.concat) {
+      auto &g = groups[seq_ctax(seqid)];
+      g.insert(g.end(), rec.pieces.begin(), rec.pieces.end());
+      taken[seqid] = 1;
+      continue;
+    }
+    if (!taken[seqid]) { taken[seqid] = 1; in.genome_seq.push_back(seqid); in.lens.push_back(len); }
+    else in.lens.back() += len;                          // (file level only: the file's records add up, Builder.hpp:159-163)
+    place(rec.pieces);
+  }
+  if (so.concat) {
+    for (const auto &kv : groups) {                      // ascending compact tax id (Builder.hpp:196-209); extra names under _nodeCnt
+      const uint64_t before = n;
+      place(kv.second);
+      if (n == before) continue;
+      in.genome_seq.push_back(kv.first);
+      in.lens.push_back(n - before);
+    }
+    in.taxid_as_seqid = true;
+  }
+  if (in.genome_seq.empty()) throw std::runtime_error("found 0 genomes in the input or after filtering.");
+}
+
+void build_index_files(const BuildInput &in_, const BuildOptions &opt, const std::string &prefix, BuildReport *rep) {
+  BuildInput in = in_;      // (a shallow struct of vectors: the text is not copied)
+  if (!in.compact) in.compact = compact_taxonomy(in);
   if (opt.protein) {
     // the reference's rule (CentrifugerBuild.cpp:221-227): a protein index built with the nucleotide default of 10 initial-lookup
     // characters gets 4 - for every caller of the library, not only for the command line
@@ -542,13 +665,16 @@ void build_index_files(const BuildInput &in, const BuildOptions &opt, const std:
   if (G == 0 || in.genome_seq.size() != G) throw std::invalid_argument("index build: the text needs at least one genome, with one sequence id and one length each");
   if (in.names.size() != in.taxids.size() + in.n_extra) throw std::invalid_argument("index build: one tax id per conversion-table sequence, none for the extra names");
   {
-    std::vector<uint8_t> seen(in.names.size(), 0);
+    // (with taxid_as_seqid the ids are compact tax ids, one more for "uncategorized")
+    const size_t n_ids = in.taxid_as_seqid ? in.compact->order.size() + 1 : in.names.size();
+    auto label = [&](uint64_t id) { return in.taxid_as_seqid ? "of compact tax id " + std::to_string(id) : in.names[id]; };
+    std::vector<uint8_t> seen(n_ids, 0);
     for (size_t g = 0; g < G; ++g) {
-      if (in.genome_seq[g] >= in.names.size()) throw std::invalid_argument("index build: a genome's sequence id is outside the name list");
-      if (seen[in.genome_seq[g]]) throw std::invalid_argument("index build: sequence " + in.names[in.genome_seq[g]] + " appears twice in the text");
+      if (in.genome_seq[g] >= n_ids) throw std::invalid_argument("index build: a genome's sequence id is outside the name list");
+      if (seen[in.genome_seq[g]]) throw std::invalid_argument("index build: sequence " + label(in.genome_seq[g]) + " appears twice in the text");
       seen[in.genome_seq[g]] = 1;
       // (Builder.hpp:143-150 filters such a genome with a warning; here the caller does the filtering - the command line does)
-      if (in.lens[g] < (uint64_t)w + 1) throw std::invalid_argument("index build: genome " + in.names[in.genome_seq[g]] + " is shorter than --ftabchars + 1");
+      if (in.lens[g] < (uint64_t)w + 1) throw std::invalid_argument("index build: genome " + label(in.genome_seq[g]) + " is shorter than --ftabchars + 1");
     }
   }
   std::vector<uint64_t> psum(G + 1, 0);
@@ -559,15 +685,21 @@ void build_index_files(const BuildInput &in, const BuildOptions &opt, const std:
 
   // (the text must be upper-case ACGT only - SequenceCompactor.hpp:59-84 drops everything else before the text is formed, so does
   // the command line; the device checks it while packing the text, no host copy is made)
-  const char *lp = strchr(kAcgt, (char)in.text[n - 1]);
-  if (!lp || !in.text[n - 1]) throw std::runtime_error("index build: the text must be upper-case ACGT only");
-  const uint8_t last_code = (uint8_t)(lp - kAcgt);
+  uint8_t last_code = 0;                   // (a packed text: read from the device's words below)
+  if (!in.take_packed_text) {
+    const char *lp = strchr(kAcgt, (char)in.text[n - 1]);
+    if (!lp || !in.text[n - 1]) throw std::runtime_error("index build: the text must be upper-case ACGT only");
+    last_code = (uint8_t)(lp - kAcgt);
+  }
 
   // ---- suffix array and what is read off it (device)
   std::vector<uint64_t> want;              // selectedSA: the row of text position psum[g+1] - w - 1 for every genome boundary (Builder.hpp:224-234)
   for (size_t g = 0; g + 1 < G; ++g) if (psum[g + 1] >= (uint64_t)w + 1) want.push_back(psum[g + 1] - w - 1);
   SaProducts sa;
-  build_sa_products(in.text, n, opt.device, rate, w, psum, want, sa, say);
+  if (in.take_packed_text) {
+    build_sa_products_packed(in.take_packed_text(), n, opt.device, rate, w, psum, want, sa, say);
+    last_code = sa.last_code;
+  } else build_sa_products(in.text, n, opt.device, rate, w, psum, want, sa, say);
   say("suffix array + products: " + std::to_string(sa.seconds_sa) + " + " + std::to_string(sa.seconds_products) + " s");
   std::map<uint64_t, uint64_t> sel;
   for (size_t k = 0; k < want.size(); ++k) {
@@ -668,7 +800,7 @@ void build_index_files(const BuildInput &in, const BuildOptions &opt, const std:
     o.raw(&zero, 1);                                             // hasEndMarker = false
     o.close();
   }
-  write_taxonomy(prefix + ".2.cfr", in);
+  write_taxonomy(prefix + ".2.cfr", in, *in.compact);
   {
     Out o(prefix + ".3.cfr");
     std::map<uint64_t, uint64_t> by_id;                        // Builder.hpp:300-305: the std::map<seqId, length> in key order

@@ -33,6 +33,7 @@
 
 #define CFR_HIP_PREFIX "index build: "      // every HIP error of this file begins with it
 #include "cfr_hip_util.hpp"
+#include "cfr_pack_text.hpp"
 
 namespace cfr {
 namespace {
@@ -51,28 +52,7 @@ constexpr uint32_t kBinBits = 14;                 // phase-1 chunks are unions o
 constexpr uint64_t kChunkDefault = 1ull << 28;    // rows per sort
 // composite key of phase 2 = group offset in the span (<= 28 bits, top) : second key (rank_bits = bits of n + 2^27, low)
 
-// ---- text ------------------------------------------------------------------------------------------------------------
-// ASCII text (a piece starting at a multiple of 32) -> packed words; *bad is raised when a character is not an upper-case A,C,G,T
-__global__ void k_pack_text(const uint8_t *text, uint64_t count, uint64_t *words, unsigned int *bad) {
-  const uint64_t wI = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (wI * 32 >= count) return;
-  uint64_t w = 0;
-  const uint64_t base = wI * 32;
-  for (uint32_t k = 0; k < 32 && base + k < count; ++k) {
-    const uint32_t ch = text[base + k];
-    const uint32_t c = ch == 'A' ? 0u : ch == 'C' ? 1u : ch == 'G' ? 2u : ch == 'T' ? 3u : 4u;
-    if (c > 3u) *bad = 1u;
-    w |= (uint64_t)(c & 3u) << (62 - 2 * k);
-  }
-  words[wI] = w;
-}
-__device__ __forceinline__ uint64_t key32(const uint64_t *T, uint64_t pos) {
-  const uint32_t o = (uint32_t)pos & 31u;
-  const uint64_t w0 = T[pos >> 5];
-  if (o == 0) return w0;
-  return (w0 << (2 * o)) | (T[(pos >> 5) + 1] >> (64 - 2 * o));
-}
-__device__ __forceinline__ uint32_t sym_at(const uint64_t *T, uint64_t pos) { return (uint32_t)(T[pos >> 5] >> (62 - 2 * (pos & 31))) & 3u; }
+// ---- text: k_pack_text, key32, sym_at (cfr_pack_text.hpp) ---------------------------------------------------------------
 
 // ---- phase 1 ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_hist(const uint64_t *T, uint64_t n, unsigned long long *hist) {
@@ -238,9 +218,13 @@ inline unsigned grid_of(uint64_t n) { return std::max(1u, grid_for(n)); }      /
 
 }  // namespace
 
-void build_sa_products(const uint8_t *text, uint64_t n, int device, uint32_t sample_rate, uint32_t w,
-                       const std::vector<uint64_t> &psum, const std::vector<uint64_t> &want_pos, SaProducts &out,
-                       const std::function<void(const std::string &)> &log) {
+// text: n ASCII symbols in host memory, or nullptr: then packed is the 2-bit text in the memory of `device` ((n + 31) / 32 + 4 words, the
+// tail zero - what cfr_refseq_assemble wrote), and this function owns it from its first line on
+static void sa_products(const uint8_t *text, uint64_t *packed, uint64_t n, int device, uint32_t sample_rate, uint32_t w,
+                        const std::vector<uint64_t> &psum, const std::vector<uint64_t> &want_pos, SaProducts &out,
+                        const std::function<void(const std::string &)> &log) {
+  DevBuf<uint64_t> d_text;
+  if (!text) d_text.adopt(packed);
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw HipError{"index build: no HIP device (the writer has no CPU path)", -1};
   if (device < 0 || device >= count) throw HipError{"index build: device ordinal out of range", -1};
@@ -261,10 +245,10 @@ void build_sa_products(const uint8_t *text, uint64_t n, int device, uint32_t sam
 
   // ---- text
   const uint64_t nwords = (n + 31) / 32;
-  DevBuf<uint64_t> d_text(nwords + 4);
+  if (text) d_text.alloc(nwords + 4);
   uint64_t *T = d_text;
-  HIP_CHECK(hipMemsetAsync(T, 0, (nwords + 4) * 8, st));
-  {
+  if (text) {
+    HIP_CHECK(hipMemsetAsync(T, 0, (nwords + 4) * 8, st));
     const uint64_t piece = 1ull << 30;
     DevBuf<uint8_t> stage(piece);
     DevBuf<unsigned int> d_bad(1);
@@ -279,6 +263,11 @@ void build_sa_products(const uint8_t *text, uint64_t n, int device, uint32_t sam
     unsigned int bad = 0;
     HIP_CHECK(hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost));
     if (bad) throw HipError{"index build: the text must be upper-case ACGT only", -2};
+  }
+  {
+    uint64_t last_word = 0;
+    HIP_CHECK(hipMemcpy(&last_word, T + ((n - 1) >> 5), 8, hipMemcpyDeviceToHost));
+    out.last_code = (uint8_t)((last_word >> (62 - 2 * ((n - 1) & 31))) & 3u);
   }
 
   uint32_t rank_bits = 1;
@@ -470,6 +459,17 @@ void build_sa_products(const uint8_t *text, uint64_t n, int device, uint32_t sam
     out.first_isa = fi;
   }
   out.seconds_products = secs(t_prod, now());
+}
+
+void build_sa_products(const uint8_t *text, uint64_t n, int device, uint32_t sample_rate, uint32_t w,
+                       const std::vector<uint64_t> &psum, const std::vector<uint64_t> &want_pos, SaProducts &out,
+                       const std::function<void(const std::string &)> &log) {
+  sa_products(text, nullptr, n, device, sample_rate, w, psum, want_pos, out, log);
+}
+void build_sa_products_packed(uint64_t *packed, uint64_t n, int device, uint32_t sample_rate, uint32_t w,
+                              const std::vector<uint64_t> &psum, const std::vector<uint64_t> &want_pos, SaProducts &out,
+                              const std::function<void(const std::string &)> &log) {
+  sa_products(nullptr, packed, n, device, sample_rate, w, psum, want_pos, out, log);
 }
 
 // ============================================================================================ byte texts (protein indexes)

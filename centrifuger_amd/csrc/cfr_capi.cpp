@@ -21,6 +21,7 @@
 #include "cfr_quant.hpp"
 #include "cfr_tail.hpp"
 #include "cfr_threads.hpp"
+#include "cfr_refseq_core.hpp"
 #include "cfr_tokenize_core.hpp"
 #include "cfr_tsv.hpp"
 #include "cfr_gz.hpp"
@@ -39,6 +40,8 @@ struct cfr_taxonomy {
 struct cfr_promote { cfr::Promote *p; };
 struct cfr_kreport { cfr::Kreport *k; };
 struct cfr_tokenizer { cfr::Tokenizer *t; };
+struct cfr_refseq { cfr::Refseq *r; bool protein; };
+struct cfr_build_selection { cfr::BuildInput in; std::vector<cfr_refseq_segment> segments; uint64_t n = 0; };
 struct cfr_tsv { cfr::Tsv *t; };
 struct cfr_gz { cfr::Gz *g; };
 struct cfr_inflate { cfr::Inflate *i; };
@@ -104,6 +107,14 @@ std::set<const cfr_tokenizer *> g_tokenizer_live;
 bool tokenizer_live(const cfr_tokenizer *h) {
   std::lock_guard<std::mutex> lk(g_tokenizer_mu);
   return h && g_tokenizer_live.count(h) != 0;
+}
+
+// ... and the cfr_refseq handles
+std::mutex g_refseq_mu;
+std::set<const cfr_refseq *> g_refseq_live;
+bool refseq_live(const cfr_refseq *h) {
+  std::lock_guard<std::mutex> lk(g_refseq_mu);
+  return h && g_refseq_live.count(h) != 0;
 }
 
 // ... and the cfr_tsv handles
@@ -296,6 +307,28 @@ void cfr_build_options_default(cfr_build_options *o) {
   memset(o, 0, sizeof(*o));
   o->ftab_chars = 10; o->offrate = 4;
 }
+// the conversion table and the taxonomy files of a cfr_build_input (not its genomes, not its text)
+static void build_input_tables(const cfr_build_input *in, cfr::BuildInput &bi) {
+  for (uint64_t i = 0; i < in->n_seqs; ++i) {
+    bi.names.emplace_back(in->seq_names[i]);
+    if (i < in->n_seqs - in->n_extra) bi.taxids.push_back(in->seq_taxids[i]);
+  }
+  bi.n_extra = in->n_extra;
+  if (in->n_present_taxids && in->present_taxids) bi.present_taxids.assign(in->present_taxids, in->present_taxids + in->n_present_taxids);
+  for (uint64_t i = 0; i < in->n_nodes; ++i) bi.nodes.push_back(cfr::TaxNode{in->node_taxid[i], in->node_parent[i], in->node_rank[i] ? in->node_rank[i] : ""});
+  for (uint64_t i = 0; i < in->n_names; ++i) bi.tax_names.emplace_back(in->name_taxid[i], in->name_text[i] ? in->name_text[i] : "");
+}
+static cfr::BuildOptions build_options(const cfr_build_options *opt) {
+  cfr::BuildOptions bo;
+  if (opt) { bo.ftab_chars = opt->ftab_chars; bo.offrate = opt->offrate; bo.device = opt->device; bo.threads = opt->threads; bo.rbbwt_b = opt->rbbwt_b; bo.verbose = opt->verbose != 0; bo.protein = opt->protein != 0; }
+  return bo;
+}
+static void build_report(const cfr::BuildReport &rep, cfr_build_report *report) {
+  if (!report) return;
+  report->n = rep.n; report->block_size = rep.block_size; report->first_isa = rep.first_isa;
+  report->seconds_sa = rep.seconds_sa; report->seconds_total = rep.seconds_total; report->rounds = rep.rounds; report->pad = 0;
+}
+
 cfr_status cfr_build_index(const cfr_build_input *in, const cfr_build_options *opt, const char *out_prefix, cfr_build_report *report) {
   if (!in || !out_prefix) return bad_arg("cfr_build_index: null argument");
   if (!in->n_seqs || !in->seq_names || !in->seq_taxids || !in->text) return bad_arg("cfr_build_index: empty input");
@@ -305,12 +338,7 @@ cfr_status cfr_build_index(const cfr_build_input *in, const cfr_build_options *o
     return bad_arg("cfr_build_index: taxonomy arrays missing");
   return guarded([&]() -> cfr_status {
     cfr::BuildInput bi;
-    for (uint64_t i = 0; i < in->n_seqs; ++i) {
-      bi.names.emplace_back(in->seq_names[i]);
-      if (i < in->n_seqs - in->n_extra) bi.taxids.push_back(in->seq_taxids[i]);
-    }
-    bi.n_extra = in->n_extra;
-    if (in->n_present_taxids && in->present_taxids) bi.present_taxids.assign(in->present_taxids, in->present_taxids + in->n_present_taxids);
+    build_input_tables(in, bi);
     if (in->n_genomes) {
       bi.genome_seq.assign(in->genome_seq, in->genome_seq + in->n_genomes);
       bi.lens.assign(in->genome_lens, in->genome_lens + in->n_genomes);
@@ -318,16 +346,137 @@ cfr_status cfr_build_index(const cfr_build_input *in, const cfr_build_options *o
       for (uint64_t i = 0; i < in->n_seqs; ++i) { bi.genome_seq.push_back(i); bi.lens.push_back(in->seq_lens[i]); }
     }
     bi.text = in->text;
-    for (uint64_t i = 0; i < in->n_nodes; ++i) bi.nodes.push_back(cfr::TaxNode{in->node_taxid[i], in->node_parent[i], in->node_rank[i] ? in->node_rank[i] : ""});
-    for (uint64_t i = 0; i < in->n_names; ++i) bi.tax_names.emplace_back(in->name_taxid[i], in->name_text[i] ? in->name_text[i] : "");
-    cfr::BuildOptions bo;
-    if (opt) { bo.ftab_chars = opt->ftab_chars; bo.offrate = opt->offrate; bo.device = opt->device; bo.threads = opt->threads; bo.rbbwt_b = opt->rbbwt_b; bo.verbose = opt->verbose != 0; bo.protein = opt->protein != 0; }
+    cfr::BuildReport rep;
+    cfr::build_index_files(bi, build_options(opt), out_prefix, &rep);
+    build_report(rep, report);
+    return CFR_OK;
+  });
+}
+
+// ---- the reference text of the index writer (cfr_refseq_core.hpp), the selection, and the build from the assembled text ----
+cfr_status cfr_refseq_open(int device, int protein, cfr_refseq **out) {
+  if (!out) return bad_arg("cfr_refseq_open: null argument");
+  *out = nullptr;
+  if (device < -1) return bad_arg("cfr_refseq_open: device is a HIP ordinal, or -1 for the host twin");
+  if (device >= 0 && protein) return bad_arg("cfr_refseq_open: protein text goes through the host twin (device -1)");
+  return guarded([&]() -> cfr_status {
+    std::unique_ptr<cfr_refseq> h(new cfr_refseq{nullptr, protein != 0});
+    h->r = device < 0 ? cfr::make_refseq_host(protein != 0) : cfr::make_refseq_device(device);
+    { std::lock_guard<std::mutex> lk(g_refseq_mu); g_refseq_live.insert(h.get()); }
+    *out = h.release();
+    return CFR_OK;
+  });
+}
+cfr_status cfr_refseq_feed(cfr_refseq *h, const uint8_t *text, uint64_t len, int at_line_start, int final, cfr_refseq_info *info) {
+  if (!refseq_live(h)) return bad_arg("cfr_refseq_feed: not an open cfr_refseq handle");
+  if (!info || (len && !text)) return bad_arg("cfr_refseq_feed: null argument");
+  if (len >> 32) return bad_arg("cfr_refseq_feed: len must be below 2^32 (offsets inside a chunk are 32 bits wide): hand the file over in pieces");
+  return guarded([&]() -> cfr_status {
+    // (RefseqCapacity is a std::runtime_error of its own so that the host twin builds without the device headers)
+    try { h->r->feed(text, len, at_line_start, final, info); } catch (const cfr::RefseqCapacity &e) { throw cfr::CapacityError{e.what()}; }
+    return CFR_OK;
+  });
+}
+cfr_status cfr_refseq_fetch(cfr_refseq *h, cfr_refseq_record *records) {
+  if (!refseq_live(h)) return bad_arg("cfr_refseq_fetch: not an open cfr_refseq handle");
+  return guarded([&]() -> cfr_status { h->r->fetch(records); return CFR_OK; });
+}
+cfr_status cfr_refseq_assemble(cfr_refseq *h, const cfr_refseq_segment *segments, uint64_t n_segments, uint64_t n) {
+  if (!refseq_live(h)) return bad_arg("cfr_refseq_assemble: not an open cfr_refseq handle");
+  if (n_segments && !segments) return bad_arg("cfr_refseq_assemble: null argument");
+  return guarded([&]() -> cfr_status { h->r->assemble(segments, n_segments, n); return CFR_OK; });
+}
+cfr_status cfr_refseq_text(cfr_refseq *h, uint8_t *ascii_out) {
+  if (!refseq_live(h)) return bad_arg("cfr_refseq_text: not an open cfr_refseq handle");
+  if (!ascii_out) return bad_arg("cfr_refseq_text: null argument");
+  return guarded([&]() -> cfr_status { h->r->text(ascii_out); return CFR_OK; });
+}
+cfr_status cfr_refseq_get_stats(cfr_refseq *h, cfr_refseq_stats *st) {
+  if (!refseq_live(h)) return bad_arg("cfr_refseq_get_stats: not an open cfr_refseq handle");
+  if (!st) return bad_arg("cfr_refseq_get_stats: null argument");
+  h->r->stats(st);
+  return CFR_OK;
+}
+void cfr_refseq_close(cfr_refseq *h) {
+  {
+    std::lock_guard<std::mutex> lk(g_refseq_mu);
+    if (!h || !g_refseq_live.erase(h)) return;
+  }
+  delete h->r;
+  delete h;
+}
+
+size_t cfr_file_base_name(const char *path, char *out, size_t cap) {
+  const std::string b = cfr::file_base_name(path ? path : "");
+  if (out && cap) { const size_t k = std::min(b.size(), cap - 1); memcpy(out, b.data(), k); out[k] = 0; }
+  return b.size();
+}
+
+cfr_status cfr_build_select(const cfr_build_input *in, const cfr_select_options *so, const cfr_select_record *records, uint64_t n_records,
+                            const cfr_select_piece *pieces, uint64_t n_pieces, cfr_build_selection **out) {
+  if (!in || !so || !out || (n_records && !records) || (n_pieces && !pieces)) return bad_arg("cfr_build_select: null argument");
+  *out = nullptr;
+  if (in->n_extra) return bad_arg("cfr_build_select: the input is the conversion table alone, without extra names");
+  if ((in->n_seqs && (!in->seq_names || !in->seq_taxids)) || (in->n_nodes && (!in->node_taxid || !in->node_parent || !in->node_rank)) ||
+      (in->n_names && (!in->name_taxid || !in->name_text)))
+    return bad_arg("cfr_build_select: table or taxonomy arrays missing");
+  return guarded([&]() -> cfr_status {
+    std::unique_ptr<cfr_build_selection> sel(new cfr_build_selection);
+    build_input_tables(in, sel->in);
+    std::vector<cfr::SelectRecord> recs((size_t)n_records);
+    for (uint64_t k = 0; k < n_records; ++k) {
+      recs[k].id = records[k].id ? records[k].id : "";
+      recs[k].file = records[k].file ? records[k].file : "";
+      if (records[k].first_piece > n_pieces || records[k].n_pieces > n_pieces - records[k].first_piece) throw std::invalid_argument("cfr_build_select: a record's pieces lie outside the piece list");
+      for (uint64_t q = 0; q < records[k].n_pieces; ++q) recs[k].pieces.push_back(cfr::SelectPiece{pieces[records[k].first_piece + q].src, pieces[records[k].first_piece + q].len});
+    }
+    cfr::SelectOptions o;
+    o.file_level = so->file_level != 0; o.concat = so->concat_tax_genome != 0; o.ignore_uncategorized = so->ignore_uncategorized != 0; o.protein = so->protein != 0;
+    o.subset_tax = so->subset_tax; o.ftab_chars = so->ftab_chars;
+    std::vector<cfr::SelectSegment> segs;
+    cfr::select_genomes(sel->in, o, recs, segs, sel->n);
+    for (const auto &g : segs) sel->segments.push_back(cfr_refseq_segment{g.src, g.len, g.dst});
+    *out = sel.release();
+    return CFR_OK;
+  });
+}
+cfr_status cfr_build_selection_get(const cfr_build_selection *s, const cfr_refseq_segment **segments, uint64_t *n_segments, uint64_t *n, uint64_t *n_genomes, uint64_t *n_extra) {
+  if (!s) return bad_arg("cfr_build_selection_get: null argument");
+  if (segments) *segments = s->segments.data();
+  if (n_segments) *n_segments = s->segments.size();
+  if (n) *n = s->n;
+  if (n_genomes) *n_genomes = s->in.genome_seq.size();
+  if (n_extra) *n_extra = s->in.n_extra;
+  return CFR_OK;
+}
+void cfr_build_selection_free(cfr_build_selection *s) { delete s; }
+
+cfr_status cfr_build_index_assembled(cfr_refseq *h, const cfr_build_input *in, const cfr_build_options *opt, const char *out_prefix, cfr_build_report *report) {
+  if (!refseq_live(h)) return bad_arg("cfr_build_index_assembled: not an open cfr_refseq handle");
+  if (!in || !out_prefix) return bad_arg("cfr_build_index_assembled: null argument");
+  if (!in->selection && (!in->n_seqs || !in->seq_names || !in->seq_taxids || !in->n_genomes || !in->genome_seq || !in->genome_lens))
+    return bad_arg("cfr_build_index_assembled: without a selection the input names the genomes of the text itself");
+  return guarded([&]() -> cfr_status {
+    cfr::BuildInput bi;
+    if (in->selection) bi = static_cast<const cfr_build_selection *>(in->selection)->in;
+    else {
+      build_input_tables(in, bi);
+      bi.genome_seq.assign(in->genome_seq, in->genome_seq + in->n_genomes);
+      bi.lens.assign(in->genome_lens, in->genome_lens + in->n_genomes);
+    }
+    const cfr::BuildOptions bo = build_options(opt);
+    if (bo.protein != h->protein) throw std::invalid_argument("cfr_build_index_assembled: the handle and the options disagree about protein");
+    uint64_t total = 0;
+    for (uint64_t l : bi.lens) total += l;
+    if (total != h->r->text_len()) throw std::invalid_argument("cfr_build_index_assembled: the genomes' lengths do not add up to the assembled text");
+    if (h->r->device() >= 0) {
+      if (h->r->device() != bo.device) throw std::invalid_argument("cfr_build_index_assembled: the text was assembled on another device than the one that is to sort it");
+      cfr::Refseq *r = h->r;
+      bi.take_packed_text = [r]() { return r->release_device_text(); };
+    } else bi.text = h->r->host_text();
     cfr::BuildReport rep;
     cfr::build_index_files(bi, bo, out_prefix, &rep);
-    if (report) {
-      report->n = rep.n; report->block_size = rep.block_size; report->first_isa = rep.first_isa;
-      report->seconds_sa = rep.seconds_sa; report->seconds_total = rep.seconds_total; report->rounds = rep.rounds; report->pad = 0;
-    }
+    build_report(rep, report);
     return CFR_OK;
   });
 }

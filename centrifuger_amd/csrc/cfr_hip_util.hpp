@@ -49,6 +49,8 @@ template <class T, class Mem> class OwnedBuf {
   ~OwnedBuf() { reset(); }
   void alloc(size_t n) { reset(); p_ = (T *)Mem::alloc(std::max<size_t>(n * sizeof(T), 16)); }
   void reset() { if (p_) Mem::free(p_); p_ = nullptr; }
+  void adopt(T *p) { reset(); p_ = p; }                // memory of the same kind that another owner has released
+  T *release() { T *p = p_; p_ = nullptr; return p; }
   T *get() const { return p_; }
   operator T *() const { return p_; }
 

@@ -805,6 +805,7 @@ typedef struct {
    * (Taxonomy.hpp:275-300), also one that no sequence ends up with (a name listed twice gets the LCA of its ids) */
   uint64_t n_present_taxids;
   const uint64_t *present_taxids;
+  const void *selection;            /* cfr_build_index_assembled only: the cfr_build_selection made from this input, or NULL */
 } cfr_build_input;
 typedef struct {
   int32_t ftab_chars;   /* --ftabchars, default 10 */
@@ -824,6 +825,69 @@ typedef struct {
 } cfr_build_report;
 void cfr_build_options_default(cfr_build_options *o);
 cfr_status cfr_build_index(const cfr_build_input *in, const cfr_build_options *opt, const char *out_prefix, cfr_build_report *report);
+
+/* ---- the reference text of the index writer: filter and assemble (csrc/cfr_refseq_core.hpp states the grammar) ----
+ * The front end of bin/centrifuger-build: the bytes of the reference files go in chunk by chunk, the symbols the index keeps come
+ * out as one stream U, and cfr_refseq_assemble copies segments of U - records dropped, records regrouped - into the text T of the
+ * index, in the HBM of the GPU that sorts its suffixes.
+ * cfr_refseq_open: device >= 0: the kernels of cfr_refseq.hip on that GPU (nucleotide only: protein is CFR_ERR_ARG there;
+ *   CFR_ERR_NO_DEVICE without the GPU: no fall-back); device = -1: the host twin, no GPU is touched, U and T are ASCII.
+ * cfr_refseq_feed: one chunk of one file, len below 2^32.  A chunk never begins inside a header line; at_line_start: its first byte
+ *   begins a line (a file's first chunk: 1; later chunks: what the previous call returned in info).  final: the file ends with this
+ *   chunk.  A chunk that ends inside a header line without final is looked at up to that '>' (info->consumed): continue there.  A
+ *   header line that fills a whole chunk that is not final is CFR_ERR_CAPACITY.
+ * cfr_refseq_fetch: the info->n_records records of the last feed.
+ * cfr_refseq_assemble: segments (src symbol in U, length, dst symbol in T) sorted by dst, none empty, covering [0, n) exactly; U is
+ *   freed, no further feed.  cfr_refseq_text: T as n ASCII bytes.
+ * cfr_build_index_assembled: cfr_build_index with the text taken from the handle (in->text is not read; a device handle must sit
+ *   on opt->device and gives its T away).  in->selection: what cfr_build_select returned, or NULL (then in->genome_* describe T).
+ * A handle is used by one thread at a time; a handle that is not open is CFR_ERR_ARG. */
+typedef struct cfr_refseq cfr_refseq;
+typedef struct { uint32_t header, header_len, id_len, kept; } cfr_refseq_record;   /* offset of the '>' in the chunk; bytes of the header line without its '\n'; bytes of the id behind the '>'; symbols kept up to the next header */
+typedef struct {
+  uint64_t n_records, consumed;
+  uint64_t lead_kept;      /* kept symbols before the chunk's first header: they continue the previous chunk's last record */
+  uint64_t kept;           /* kept symbols of the chunk, lead_kept included */
+  uint64_t u_start;        /* where the chunk's symbols begin in U (a multiple of 32) */
+  int32_t at_line_start, pad;
+  double device_ms;
+} cfr_refseq_info;
+typedef struct { uint64_t src, len, dst; } cfr_refseq_segment;
+typedef struct { double feed_ms, copy_in_ms, assemble_ms; } cfr_refseq_stats;      /* sums over the feeds (copy_in_ms is part of feed_ms); the last assemble */
+cfr_status cfr_refseq_open(int device, int protein, cfr_refseq **out);
+cfr_status cfr_refseq_feed(cfr_refseq *h, const uint8_t *text, uint64_t len, int at_line_start, int final, cfr_refseq_info *info);
+cfr_status cfr_refseq_fetch(cfr_refseq *h, cfr_refseq_record *records);
+cfr_status cfr_refseq_assemble(cfr_refseq *h, const cfr_refseq_segment *segments, uint64_t n_segments, uint64_t n);
+cfr_status cfr_refseq_text(cfr_refseq *h, uint8_t *ascii_out);
+cfr_status cfr_refseq_get_stats(cfr_refseq *h, cfr_refseq_stats *st);
+void cfr_refseq_close(cfr_refseq *h);
+
+/* ---- selection: which records of the reference files become which genomes of the text (Builder::Build, Builder.hpp:104-211) ----
+ * records: every FASTA record in reading order - its id, its file, and where its kept symbols lie in U (pieces first_piece ..
+ * first_piece + n_pieces of `pieces`: a record cut by a chunk end has more than one).  in: the conversion table (seq_names, seq_taxids,
+ * present_taxids; with file_level the file list with Utils::GetFileBaseName names - cfr_file_base_name), nodes and names; its genome
+ * fields are not read.  The result holds the segments for cfr_refseq_assemble and, behind in->selection, everything
+ * cfr_build_index_assembled needs: extra names, genomes, the compact tax ids (computed once, shared with the writer of .2.cfr).
+ * Nothing left to index: CFR_ERR_ARG with the reference's "found 0 genomes" message. */
+typedef struct cfr_build_selection cfr_build_selection;
+typedef struct { const char *id; const char *file; uint64_t first_piece, n_pieces; } cfr_select_record;
+typedef struct { uint64_t src, len; } cfr_select_piece;
+typedef struct {
+  int32_t file_level;              /* a two-column -l list is the conversion table: names are file base names, a file's records add into one genome */
+  int32_t concat_tax_genome;       /* --concat-tax-genome */
+  int32_t ignore_uncategorized;    /* --ignore-uncategorized-genome */
+  int32_t protein;
+  uint64_t subset_tax;             /* --subset-tax, 0: off */
+  int32_t ftab_chars, pad;
+} cfr_select_options;
+cfr_status cfr_build_select(const cfr_build_input *in, const cfr_select_options *so, const cfr_select_record *records, uint64_t n_records,
+                            const cfr_select_piece *pieces, uint64_t n_pieces, cfr_build_selection **out);
+/* the segments (valid until cfr_build_selection_free), the length of the text, its genomes and the extra names */
+cfr_status cfr_build_selection_get(const cfr_build_selection *s, const cfr_refseq_segment **segments, uint64_t *n_segments, uint64_t *n,
+                                   uint64_t *n_genomes, uint64_t *n_extra);
+void cfr_build_selection_free(cfr_build_selection *s);
+size_t cfr_file_base_name(const char *path, char *out, size_t cap);      /* returns the length of the name; out (may be NULL) gets at most cap - 1 bytes and a 0 */
+cfr_status cfr_build_index_assembled(cfr_refseq *h, const cfr_build_input *in, const cfr_build_options *opt, const char *out_prefix, cfr_build_report *report);
 
 #ifdef __cplusplus
 }

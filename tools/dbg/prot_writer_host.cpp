@@ -16,6 +16,8 @@
 namespace cfr {
 void build_sa_products(const uint8_t *, uint64_t, int, uint32_t, uint32_t, const std::vector<uint64_t> &, const std::vector<uint64_t> &, SaProducts &,
                        const std::function<void(const std::string &)> &) { throw std::runtime_error("nucleotide texts need the device"); }
+void build_sa_products_packed(uint64_t *, uint64_t, int, uint32_t, uint32_t, const std::vector<uint64_t> &, const std::vector<uint64_t> &, SaProducts &,
+                              const std::function<void(const std::string &)> &) { throw std::runtime_error("nucleotide texts need the device"); }
 void build_sa_bytes(const uint8_t *codes, uint64_t n, int, std::vector<uint32_t> &sa, double *seconds, int *rounds) {
   sa.resize(n);
   for (uint64_t i = 0; i < n; ++i) sa[i] = (uint32_t)i;
